@@ -5,7 +5,12 @@ Workload (BASELINE.json configs[1]; configs[2] at N=8): the reference's 16-organ
 synthetic CT-like volumes, random-init weights. One step = forward + EDiceLoss_partial(16) (uce) + backward
 (gradient all-reduce over RCCL inside the backward when N > 1) + SGD(momentum 0.9, wd 1e-4).
 
-Prints ONE JSON line on rank 0. `roofline` is the ring kernel with the largest time per step among the full-patch
+Prints ONE JSON line on rank 0. A plain run sets up, warms up, times `--steps` steps and prints the line (`value`,
+`ms_per_step`); `--dump-outputs DIR` also writes what the last timed step left its caller (loss, updated weights,
+gradients) as DIR/<name>.npy, identical inputs from run to run. The legs below run only with `--full` (each can be
+switched off there with its `--no-*` flag); without it their keys are null.
+
+`roofline` is the ring kernel with the largest time per step among the full-patch
 96^3 rings (the 32->32 3^3 convs: forward, data gradient with the fused GroupNorm-backward partials, and the stride-1
 weight gradient), each launch timed with HIP events on the stream it runs on; the others are listed in
 `roofline.rings`. `infer_cfg5` is BASELINE configs[4] (sliding-window inference of a 256x512x512 volume, 80 tiles,
@@ -46,10 +51,18 @@ def parse():
     p.add_argument("--modality", default="ct", choices=["ct", "mixed"],
                    help="mixed = BASELINE configs[3]: per GPU one CT-normalised and one z-scored MRI-like patch "
                         "(MOTSDataset.py:171-185), the batch's mask[0] applied to both (loss_partial.py:87)")
-    p.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    p.add_argument("--no-roofline", action="store_true")
-    p.add_argument("--no-infer", action="store_true", help="skip the configs[4] sliding-window inference leg")
-    p.add_argument("--no-mixed", action="store_true", help="skip the configs[3] (CT + MRI batch) step leg at N=1")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run the other legs: ring-kernel roofline (an eager probe pass of the "
+                        "same steps), configs[3] mixed-modality step, configs[4] sliding-window inference, CPU baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step left its caller as DIR/<name>.npy (float32): loss, and seeded "
+                        "fixed samples of the updated weights and of their gradients")
+    p.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg")
+    p.add_argument("--no-roofline", action="store_true", help="with --full: skip the ring-kernel roofline leg")
+    p.add_argument("--no-infer", action="store_true",
+                   help="with --full: skip the configs[4] sliding-window inference leg")
+    p.add_argument("--no-mixed", action="store_true",
+                   help="with --full: skip the configs[3] (CT + MRI batch) step leg at N=1")
     p.add_argument("--force-buckets", action="store_true",
                    help="N=1 only: RCCL (nccl backend) at world size 1 with U3DDataParallel(force_buckets=True), i.e. "
                         "the bucketed all-reduces launched from inside the backward and the collective-tolerant kernel "
@@ -329,6 +342,31 @@ def mixed_leg(a, make_step, opt, device, rank):
             "launch": "eager" if a.eager else "hipgraph", "loss": round(float(loss), 6)}
 
 
+DUMP_SAMPLE = 4 * 1024 * 1024  # elements kept of each flattened parameter-sized output (16 MB as float32)
+
+
+def dump_outputs(dirname, loss, model):
+    """--dump-outputs: what the last timed step handed its caller, as float32 .npy files: `loss` (the returned value,
+    shape [1]), `params` (the weights after the step's SGD update) and `grads` (the gradients it left in .grad; zeros
+    where a parameter got none), each flattened in model.parameters() order and, where longer than DUMP_SAMPLE,
+    gathered at the same seeded element indices in every run."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    ps = list(model.parameters())
+    flat = {"params": torch.cat([p.detach().reshape(-1).float() for p in ps]),
+            "grads": torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float()
+                                for p in ps])}
+    n = flat["params"].numel()
+    idx = None
+    if n > DUMP_SAMPLE:
+        g = torch.Generator(device="cpu").manual_seed(0)
+        idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=g).sort().values
+    np.save(os.path.join(dirname, "loss.npy"), loss.detach().float().reshape(1).cpu().numpy())
+    for name, t in flat.items():
+        t = t.cpu()
+        np.save(os.path.join(dirname, name + ".npy"), (t if idx is None else t[idx]).numpy())
+
+
 def spawn_ranks(n):
     """`bench.py --gpus N` without a launcher: start N child ranks (RANK / LOCAL_RANK / WORLD_SIZE, rendezvous on
     127.0.0.1) before this process touches the GPU, pass their output through, exit with the worst status."""
@@ -478,8 +516,10 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
     loss_v = float(loss)
+    if a.dump_outputs and rank == 0:  # before any other leg runs further steps on this model
+        dump_outputs(a.dump_outputs, loss, model)
     _ops.PROBE = None
-    if not a.no_roofline:  # (every rank: the step may hold collectives)
+    if a.full and not a.no_roofline:  # (every rank: the step may hold collectives)
         # the ring kernels' live timing (HIP events around every launch) comes from an eager pass of the same step
         # right after the timed region: graph replay has no per-launch events, and the events' host cost (~0.4 ms per
         # eager step, r04) stays out of the timed steps
@@ -501,12 +541,12 @@ def main():
     vox = world * a.batch * a.patch ** 3 * a.steps / dt
 
     mixed = None
-    if world == 1 and a.modality == "ct" and not a.no_mixed:
+    if a.full and world == 1 and a.modality == "ct" and not a.no_mixed:
         mixed = mixed_leg(a, make_step, opt, device, rank)
     roof = None
     cpu = None
     infer = None
-    if rank == 0 and not a.no_roofline:
+    if a.full and rank == 0 and not a.no_roofline:
         roof = dominant_kernel_roofline(device, a.batch, a.patch, groups)
         if probe_pass:
             roof["probe_pass"] = probe_pass
@@ -514,9 +554,9 @@ def main():
                 roof["timing"] = "HIP events, every launch of the " + probe_pass
         step_gflop = STEP_GFLOP_PER_SAMPLE * a.batch * (a.patch / 96) ** 3
         roof["step_mfma_frac"] = round(step_gflop / (ms * 1e-3) / 1e3 / PEAK_BF16_TFLOPS, 4)
-    if rank == 0 and world == 1 and not a.no_infer:
+    if a.full and rank == 0 and world == 1 and not a.no_infer:
         infer = infer_cfg5(device)
-    if rank == 0 and world == 1 and not a.no_cpu:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu:
         cpu = cpu_baseline(a.batch, a.patch)
     if rank == 0:
         out = {

@@ -500,6 +500,42 @@ def test_bench_launch_mode_defaults():
     assert bench.launch_mode(ns(eager=True), 8) == "eager"
 
 
+def test_bench_plain_run_options_and_dump(tmp_path, monkeypatch):
+    """A plain bench run carries no extra leg (--full off by default), and --dump-outputs writes float32 loss /
+    params / grads of the model in parameter order, the same seeded sample of the long ones on every call."""
+    import sys
+    sys.path.insert(0, REPO)
+    import bench
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d"
+
+    torch.manual_seed(3)
+    m = torch.nn.Sequential(torch.nn.Linear(5, 4), torch.nn.Linear(4, 3, bias=False))
+    m[0].weight.grad = torch.randn(4, 5)
+    m[1].weight.grad = torch.randn(3, 4)   # m[0].bias has no gradient: zeros
+    flat_p = torch.cat([p.detach().reshape(-1) for p in m.parameters()]).numpy()
+    flat_g = torch.cat([m[0].weight.grad.reshape(-1), torch.zeros(4), m[1].weight.grad.reshape(-1)]).numpy()
+    bench.dump_outputs(str(tmp_path / "full"), torch.tensor(1.5), m)
+    out = {n: np.load(tmp_path / "full" / f"{n}.npy") for n in ("loss", "params", "grads")}
+    assert all(v.dtype == np.float32 for v in out.values())
+    assert out["loss"].tolist() == [1.5]
+    assert np.array_equal(out["params"], flat_p) and np.array_equal(out["grads"], flat_g)
+
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 8)     # shorter than the 36 parameters: sampled
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), torch.tensor(1.5), m)
+    s1, s2 = (np.load(tmp_path / d / "grads.npy") for d in ("s1", "s2"))
+    assert s1.shape == (8,) and np.array_equal(s1, s2)
+    p1 = np.load(tmp_path / "s1" / "params.npy")
+    assert all(any(np.array_equal(p1[i:i + 1], flat_p[j:j + 1]) and s1[i] == flat_g[j] for j in range(36))
+               for i in range(8))
+
+
 # ------------------------------------------------------------- f1: sliding-window tiles sharded over ranks
 def test_tile_plan_matches_reference_tiling_and_shards_partition_it():
     from evaluate_amos import shard_tiles, tile_plan

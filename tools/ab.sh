@@ -7,7 +7,7 @@ mkdir -p $O
 cd $R
 for i in $(seq $N); do
   for cfg in "$A" "$B"; do
-    ms=$(env $cfg timeout -k 10 200 python bench.py --no-cpu --no-roofline --steps 30 --warmup 5 2>>$O/ab.err | python -c "import json,sys; print(json.loads(sys.stdin.read().strip().splitlines()[-1])['ms_per_step'])") || exit 1
+    ms=$(env $cfg timeout -k 10 200 python bench.py --steps 30 --warmup 5 2>>$O/ab.err | python -c "import json,sys; print(json.loads(sys.stdin.read().strip().splitlines()[-1])['ms_per_step'])") || exit 1
     echo "$cfg $ms" | tee -a $O/ab.log
   done
 done

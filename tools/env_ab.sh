@@ -9,6 +9,6 @@ cd $R
 bash tools/ab.sh $TAG "$A" "$B" 3 || exit 1
 for cfg in "$A" "$B"; do
   k=$(echo "$cfg" | tr -c 'A-Za-z0-9\n' '_')
-  (cd /tmp && export TMPDIR=/tmp && export $cfg && timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_$k -o run -- python3 $R/bench.py --steps 5 --warmup 2 --no-cpu --no-roofline > $O/kt_$k.log 2>&1) || exit 1
+  (cd /tmp && export TMPDIR=/tmp && export $cfg && timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_$k -o run -- python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu --no-roofline > $O/kt_$k.log 2>&1) || exit 1
   python3 $R/tools/kstats.py "$KRX" $(find $O/kt_$k -name '*kernel_stats.csv') | sed "s|^|$k |" | tee -a $O/kernels.csv
 done

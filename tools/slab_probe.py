@@ -2,7 +2,7 @@
 import os
 import sys
 
-sys.argv = ["bench.py", "--no-cpu", "--no-roofline", "--steps", "1", "--warmup", "0"]
+sys.argv = ["bench.py", "--full", "--no-cpu", "--no-roofline", "--steps", "1", "--warmup", "0"]
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "multimodal-pl_amd"))
 from u3d import ops  # noqa: E402
