@@ -168,6 +168,39 @@ __device__ __forceinline__ float wave_sum_transposed(float (&v)[N], int lane) {
   return v[0];
 }
 
+// ------------------------------------------------------------------------- last-arriver hand-off
+// True, in every thread of the workgroup, for the workgroup whose arrival on *cnt is the total-th: the one that may
+// read what all `total` workgroups stored before they arrived. The one copy of the protocol; the contract:
+//  - every byte handed off was stored with sc1 (write-through: __hip_atomic_store relaxed / agent, or a buffer store
+//    with the sc1 bit) by a wave of a calling workgroup, before the call;
+//  - every thread of the workgroup calls it (two barriers; the drain below is each wave's own);
+//  - the last arriver reads those bytes only after the call returns and only with sc1 loads (ld_sc1,
+//    lastarriver_rowsum, buffer loads with the sc1 bit): L2-served, never a stale L1 line;
+//  - *cnt is 0 before the launch and is left 0 by the last arriver, ready for the next launch on the stream.
+// No fence: the sc1 stores are past the XCD's L2 once each wave's vmcnt(0) wait returns, the barrier puts lane 0's
+// add behind every wave's wait, and the reader bypasses L1, so nothing is left for a release or an acquire to repair
+// (MI355X microarchitecture guide, inter-workgroup visibility: the sc1-loads-for-acquire conditions and the row "one
+// lane of each storing workgroup ... the workgroup whose add came last"). A release at agent scope would write back
+// the XCD's whole L2, microseconds per call, which nobody has measured in these kernels; the order stays relaxed.
+// A kernel may call it twice (conv_small: a tile's counter, then the launch's): the flag is one LDS word shared by
+// the calls, safe because the second call begins with a barrier that every reader of the first result has passed.
+__device__ __forceinline__ bool last_arriver(unsigned* cnt, unsigned total) {
+  __shared__ unsigned s_last;
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned old = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    s_last = old == total - 1;
+    if (s_last) __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __syncthreads();
+  return s_last;
+}
+
+__device__ __forceinline__ float ld_sc1(const float* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // The combine of a launch's last-arriving workgroup over the partial rows the launch's workgroups wrote (sc1 stores):
 // out[r * K + k] (fp64, LDS) = sum over w < nw of rows[(r * nw + w) * K + k], for r < nr, k < K (K % 4 == 0).
 // L lanes per (row r, column quad), L the largest power of two <= 64 with all items in one pass of NT threads; lane l
@@ -219,6 +252,68 @@ __device__ __forceinline__ void lastarriver_rowsum(const float* rows, int nr, in
       o4[2] = a2;
       o4[3] = a3;
     }
+  }
+}
+
+// GroupNorm (mean, rstd) of one (sample, group) from its fp64 sums of values s1 and of squares s2 over m values:
+// biased variance clamped at 0, the model's eps. The mean stays fp64 for the caller that adds a shift before rounding.
+constexpr double GN_EPS = 1e-5;
+struct GnStat {
+  double mean;
+  float rstd;
+};
+__device__ __forceinline__ GnStat gn_mean_rstd(double s1, double s2, double m) {
+  const double mean = s1 / m;
+  double var = s2 / m - mean * mean;
+  if (var < 0) var = 0;
+  return GnStat{mean, (float)(1.0 / sqrt(var + GN_EPS))};
+}
+__device__ __forceinline__ void gn_store_stats(float* st /*[2]*/, double s1, double s2, double m) {
+  const GnStat r = gn_mean_rstd(s1, s2, m);
+  st[0] = (float)r.mean;
+  st[1] = r.rstd;
+}
+
+// GroupNorm backward, from the per-(sample, channel) fp64 sums cs[n * c][2] = (s1, s2) = (sum g, sum g * xhat), g = m * dA
+// with m the forward prologue's relu test x * sc + sh > 0, over M = voxels * channels-per-group values: the apply
+// coefficients of every (sample, channel), SoA coef[n][5][c]:
+//   sc, sh, alpha = rs * gamma_c, bx = -rs^2 * b_g, d = -rs * a_g + rs^2 * b_g * mu
+// with a_g = sum_{c in g} gamma_c s1_c / M, b_g = sum gamma_c s2_c / M, so that
+//   dx = alpha * m * dA + bx * x + d  ==  rs * (gamma * m * dA - a_g - xhat * b_g)   (autograd of GN, unet3D.py:44-53)
+// and dgamma_c (+)= sum_n s2, dbeta_c (+)= sum_n s1 (accp: accumulate; either may be null). NT threads stride the work;
+// cs is complete (the caller's barrier) before the call. The one copy: tests pin these expressions to fp64.
+template <int NT>
+__device__ __forceinline__ void gn_bwd_coefs(const double* cs, int n, int c, int groups, double M,
+                                             const float* __restrict__ stats, const float* __restrict__ gamma,
+                                             const float* __restrict__ beta, float* __restrict__ coef,
+                                             float* __restrict__ dgamma, float* __restrict__ dbeta, int accp) {
+  const int tid = threadIdx.x, cpg = c / groups;
+  for (int p = tid; p < n * c; p += NT) {
+    const int nn = p / c, ch = p % c, gr = ch / cpg;
+    double a = 0, bb = 0;
+    for (int k = 0; k < cpg; ++k) {
+      const int cc = gr * cpg + k;
+      a += (double)gamma[cc] * cs[2 * (nn * c + cc)];
+      bb += (double)gamma[cc] * cs[2 * (nn * c + cc) + 1];
+    }
+    const float ca = (float)(a / M), cb = (float)(bb / M);
+    const float mu = stats[(nn * groups + gr) * 2], rs = stats[(nn * groups + gr) * 2 + 1];
+    const float scv = rs * gamma[ch];
+    float* o = coef + (long long)nn * 5 * c;
+    o[ch] = scv;
+    o[c + ch] = beta[ch] - mu * scv;
+    o[2 * c + ch] = rs * gamma[ch];
+    o[3 * c + ch] = -rs * rs * cb;
+    o[4 * c + ch] = -rs * ca + rs * rs * cb * mu;
+  }
+  for (int ch = tid; ch < c; ch += NT) {
+    double tg = 0, tb = 0;
+    for (int nn = 0; nn < n; ++nn) {
+      tb += cs[2 * (nn * c + ch)];
+      tg += cs[2 * (nn * c + ch) + 1];
+    }
+    if (dgamma) dgamma[ch] = (accp ? dgamma[ch] : 0.f) + (float)tg;
+    if (dbeta) dbeta[ch] = (accp ? dbeta[ch] : 0.f) + (float)tb;
   }
 }
 

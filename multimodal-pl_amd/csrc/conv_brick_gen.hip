@@ -789,20 +789,9 @@ __global__ __launch_bounds__(GB_NT, 1) void convg_pbrick_kernel(const bf16* __re
   if constexpr (!GB) {
     if (spart != nullptr && g.fcnt != nullptr) {
       // Round 5: the GroupNorm(16) finalize (pbrick_gn_finalize_kernel's sums, one launch less) by the workgroup that
-      // arrives last: every wave drains its sc1 partial stores, one lane per workgroup adds to the arrival counter
-      // (agent scope), the last arriver reads the partials with sc1 loads (MI355X_MICROARCH.md visibility, counter
-      // row). 16 lanes per (sample, group), strided over the sample's bricks, the pairs in order, then an xor tree
-      // over the 16 lanes in fixed order: deterministic.
-      __shared__ unsigned s_last;
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (tid == 0) {
-        const unsigned old = __hip_atomic_fetch_add(g.fcnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = old == gridDim.x - 1;
-        if (s_last) __hip_atomic_store(g.fcnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      __syncthreads();
-      if (s_last) {
+      // arrives last (last_arriver; the partials above are its sc1 stores). 16 lanes per (sample, group), strided over
+      // the sample's bricks, the pairs in order, then an xor tree over the 16 lanes in fixed order: deterministic.
+      if (last_arriver(g.fcnt, gridDim.x)) {
         const int bps = g.nbd * g.nbh * g.nbw, cpg = g.cout / 16, l16 = tid & 15;
         const double m = (double)cpg * g.d * g.h * g.w;
         for (int p0 = 0; p0 < g.n * 16; p0 += GB_NT / 16) {
@@ -836,13 +825,7 @@ __global__ __launch_bounds__(GB_NT, 1) void convg_pbrick_kernel(const bf16* __re
             s1 += __shfl_xor(s1, o);
             s2 += __shfl_xor(s2, o);
           }
-          if (p < g.n * 16 && l16 == 0) {
-            const double mean = s1 / m;
-            double var = s2 / m - mean * mean;
-            if (var < 0) var = 0;
-            g.fstats[p * 2] = (float)mean;
-            g.fstats[p * 2 + 1] = (float)(1.0 / sqrt(var + 1e-5));
-          }
+          if (p < g.n * 16 && l16 == 0) gn_store_stats(g.fstats + p * 2, s1, s2, m);
         }
       }
     }
@@ -890,11 +873,7 @@ __global__ __launch_bounds__(256) void pbrick_gn_finalize_kernel(const double* _
   if (tid == 0) {
     const double t1 = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
     const double t2 = ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1];
-    const double mean = t1 / m;
-    double var = t2 / m - mean * mean;
-    if (var < 0) var = 0;
-    stats[p * 2] = (float)mean;
-    stats[p * 2 + 1] = (float)(1.0 / sqrt(var + 1e-5));
+    gn_store_stats(stats + p * 2, t1, t2, m);
   }
 }
 

@@ -722,52 +722,15 @@ __global__ __launch_bounds__(RG_NT, 1) void conv32_ring_kernel(const bf16* __res
         spart[(long long)bid * 64 + tid] = t;  // [sample][wps][channel][2]: bid = sample * wps + jw
     }
     if (g.fcnt) {
-      // Round 5: gn_bwd_parts_finalize by the workgroup that arrives last (one launch less): every wave drains, one lane
-      // per workgroup adds to the arrival counter, the last arriver sums the partial rows per (sample, channel) in fp64
-      // (8 lanes per pair strided over the sample's workgroups, then an xor tree in fixed order: deterministic) and
-      // forms the apply coefficients coef[n][5][32] and dgamma / dbeta exactly as gn_bwd_coefs does.
-      __shared__ unsigned s_last;
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (tid == 0) {
-        const unsigned old = __hip_atomic_fetch_add(g.fcnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = old == gridDim.x - 1;
-        if (s_last) __hip_atomic_store(g.fcnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      __syncthreads();
-      if (!s_last) return;
+      // Round 5: gn_bwd_parts_finalize by the workgroup that arrives last (one launch less): the last arriver sums the
+      // partial rows per (sample, channel) in fp64 (8 lanes per pair strided over the sample's workgroups, then an xor
+      // tree in fixed order: deterministic) and forms the apply coefficients coef[n][5][32] and dgamma / dbeta.
+      if (!last_arriver(g.fcnt, gridDim.x)) return;
       double* const cs = reinterpret_cast<double*>(ring);  // [n * 32][2]
       lastarriver_rowsum<RG_NT>(spart, g.n, g.wps, 64, cs);
       __syncthreads();
-      const int gcpg = 32 / g.gn_groups;
-      const double M = (double)g.d * g.h * g.w * gcpg;
-      for (int pr = tid; pr < g.n * 32; pr += RG_NT) {
-        const int nn = pr >> 5, c = pr & 31, gr = c / gcpg;
-        double a = 0, bb = 0;
-        for (int k2 = 0; k2 < gcpg; ++k2) {
-          const int cc = gr * gcpg + k2;
-          a += (double)gamma[cc] * cs[2 * (nn * 32 + cc)];
-          bb += (double)gamma[cc] * cs[2 * (nn * 32 + cc) + 1];
-        }
-        const float ca = (float)(a / M), cb = (float)(bb / M);
-        const float mu = gstat[(nn * g.gn_groups + gr) * 2], rs = gstat[(nn * g.gn_groups + gr) * 2 + 1];
-        const float scv = rs * gamma[c];
-        float* oc = g.coef + (long long)nn * 5 * 32;
-        oc[c] = scv;
-        oc[32 + c] = beta[c] - mu * scv;
-        oc[64 + c] = rs * gamma[c];
-        oc[96 + c] = -rs * rs * cb;
-        oc[128 + c] = -rs * ca + rs * rs * cb * mu;
-      }
-      if (tid < 32) {
-        double tg = 0, tb = 0;
-        for (int nn = 0; nn < g.n; ++nn) {
-          tb += cs[2 * (nn * 32 + tid)];
-          tg += cs[2 * (nn * 32 + tid) + 1];
-        }
-        if (g.dgamma) g.dgamma[tid] = (float)tg;
-        if (g.dbeta) g.dbeta[tid] = (float)tb;
-      }
+      const double M = (double)g.d * g.h * g.w * (32 / g.gn_groups);
+      gn_bwd_coefs<RG_NT>(cs, g.n, 32, g.gn_groups, M, gstat, gamma, beta, g.coef, g.dgamma, g.dbeta, 0);
     }
   } else if constexpr (GN) {
     if (spart == nullptr) return;
@@ -800,30 +763,14 @@ __global__ __launch_bounds__(RG_NT, 1) void conv32_ring_kernel(const bf16* __res
         spart[(long long)bid * 32 + tid] = t;  // [sample][wps][group][2]: bid = sample * wps + jw
     }
     if (g.fcnt) {
-      // Round 5: ring_gn_finalize_kernel's combine by the workgroup that arrives last (one launch less): every wave
-      // drains, one lane per workgroup adds to the arrival counter (agent scope), the last arriver reads the partial
-      // rows with sc1 loads; 16 lanes per (sample, group) strided over the sample's workgroups, xor tree in fixed order.
-      __shared__ unsigned s_last;
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (tid == 0) {
-        const unsigned old = __hip_atomic_fetch_add(g.fcnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = old == gridDim.x - 1;
-        if (s_last) __hip_atomic_store(g.fcnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      __syncthreads();
-      if (s_last) {
+      // Round 5: ring_gn_finalize_kernel's combine by the workgroup that arrives last (one launch less): 16 lanes per
+      // (sample, group) strided over the sample's workgroups, xor tree in fixed order.
+      if (last_arriver(g.fcnt, gridDim.x)) {
         double* const cs = reinterpret_cast<double*>(ring) + 2048;  // [n * 16][2] (past the stats rows in `red`)
         lastarriver_rowsum<RG_NT>(spart, g.n, g.wps, 32, cs);
         __syncthreads();
         const double m = 2.0 * g.d * g.h * g.w;
-        for (int p = tid; p < g.n * 16; p += RG_NT) {
-          const double mean = cs[2 * p] / m;
-          double var = cs[2 * p + 1] / m - mean * mean;
-          if (var < 0) var = 0;
-          g.fstats[p * 2] = (float)mean;
-          g.fstats[p * 2 + 1] = (float)(1.0 / sqrt(var + 1e-5));
-        }
+        for (int p = tid; p < g.n * 16; p += RG_NT) gn_store_stats(g.fstats + p * 2, cs[2 * p], cs[2 * p + 1], m);
       }
     }
   }
@@ -864,11 +811,7 @@ __global__ __launch_bounds__(256) void ring_gn_finalize_kernel(const float* __re
   if (tid == 0) {
     const double t1 = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
     const double t2 = ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1];
-    const double mean = t1 / m;
-    double var = t2 / m - mean * mean;
-    if (var < 0) var = 0;
-    stats[p * 2] = (float)mean;
-    stats[p * 2 + 1] = (float)(1.0 / sqrt(var + 1e-5));
+    gn_store_stats(stats + p * 2, t1, t2, m);
   }
 }
 
@@ -1054,13 +997,7 @@ __global__ __launch_bounds__(256) void ring_gn_finalize_q_kernel(const float* __
       for (int e = 0; e < 32; ++e) red[t][e] += red[t + st][e];
     __syncthreads();
   }
-  if (t < 16) {
-    const double mean = red[0][2 * t] / m;
-    double var = red[0][2 * t + 1] / m - mean * mean;
-    if (var < 0) var = 0;
-    stats[(nn * 16 + t) * 2] = (float)mean;
-    stats[(nn * 16 + t) * 2 + 1] = (float)(1.0 / sqrt(var + 1e-5));
-  }
+  if (t < 16) gn_store_stats(stats + (nn * 16 + t) * 2, red[0][2 * t], red[0][2 * t + 1], m);
 }
 
 extern "C" int u3d_conv32_ring_q_stats_finalize(const float* stats_ws, int n, int d, int h, int w, float* stats_out,

@@ -318,27 +318,12 @@ __global__ __launch_bounds__(S2_NT, 1) void conv_s2_ring_kernel(const bf16* __re
     const float t2 = red[((0 * 4 + cb_) * 4 + q_) * 2 + k] + red[((1 * 4 + cb_) * 4 + q_) * 2 + k];
     __hip_atomic_store(g.spart + (long long)bid * 32 + tid, t2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // sc1
   }
-  __shared__ unsigned s_last;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) {
-    const unsigned old = __hip_atomic_fetch_add(g.cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s_last = old == gridDim.x - 1;
-    if (s_last) __hip_atomic_store(g.cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __syncthreads();
-  if (!s_last) return;
+  if (!last_arriver(g.cnt, gridDim.x)) return;
   double* const cs = reinterpret_cast<double*>(smem) + 64;  // [n * 16][2] (past the wave rows in `red`)
   lastarriver_rowsum<S2_NT>(g.spart, g.n, g.wps, 32, cs);
   __syncthreads();
   const double m = 4.0 * g.od * g.oh * g.ow;  // values per group and sample: 4 channels
-  for (int pr = tid; pr < g.n * 16; pr += S2_NT) {
-    const double mean = cs[2 * pr] / m;
-    double var = cs[2 * pr + 1] / m - mean * mean;
-    if (var < 0) var = 0;
-    g.stats[pr * 2] = (float)mean;
-    g.stats[pr * 2 + 1] = (float)(1.0 / sqrt(var + 1e-5));
-  }
+  for (int pr = tid; pr < g.n * 16; pr += S2_NT) gn_store_stats(g.stats + pr * 2, cs[2 * pr], cs[2 * pr + 1], m);
 }
 
 }  // namespace u3d

@@ -258,19 +258,11 @@ __global__ __launch_bounds__(SC_NT, 512 / SC_NT) void conv_small_kernel(const bf
     if (!g.cnt) return;  // the separate small_reduce_kernel sums the slabs
     // ---- in-kernel split-K combine (round 5): the workgroup that completes its output tile last sums the tile's
     // nks slabs in slab order (bitwise the small_reduce_kernel sums), adds the residual and stores y
-    __shared__ unsigned s_last;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains its sc1 stores
-    __syncthreads();
     ts.mark<2>();
     const int tile = bid / g.nks;
-    if (tid == 0) {
-      const unsigned old = __hip_atomic_fetch_add(g.cnt + tile, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      s_last = old == (unsigned)(g.nks - 1);
-      if (s_last) __hip_atomic_store(g.cnt + tile, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
+    const bool tile_last = last_arriver(g.cnt + tile, (unsigned)g.nks);
     ts.mark<3>();
-    if (!s_last) return;
+    if (!tile_last) return;
     float ls[8], lq[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) ls[k] = lq[k] = 0.f;
@@ -387,6 +379,7 @@ __global__ __launch_bounds__(SC_NT, 512 / SC_NT) void conv_small_kernel(const bf
     else
       combine(std::integral_constant<int, 8>{});
     ts.mark<4>();
+    const int ntiles = (int)(gridDim.x / g.nks);  // the second hand-off's counter follows the per-tile ones
     if (g.gbx) {
       // per channel of the tile over the workgroup: lanes with the same tid & 7 (xor 8, 16, 32), then the waves in order
 #pragma unroll
@@ -413,52 +406,17 @@ __global__ __launch_bounds__(SC_NT, 512 / SC_NT) void conv_small_kernel(const bf
         __hip_atomic_store(g.gbparts + (((long long)nn * nbr + brick) * g.cout + co0) * 2 + tid, t2, __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);  // sc1
       }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
       ts.mark<5>();
-      const int ntiles = (int)(gridDim.x / g.nks);
-      if (tid == 0) {
-        const unsigned old = __hip_atomic_fetch_add(g.cnt + ntiles, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = old == (unsigned)(ntiles - 1);
-        if (s_last) __hip_atomic_store(g.cnt + ntiles, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      __syncthreads();
+      const bool last = last_arriver(g.cnt + ntiles, (unsigned)ntiles);
       ts.mark<6>();
       store_y();
-      if (!s_last) return;
-      // gn_bwd_parts_finalize + gn_bwd_coefs: per (n, c) fp64 sums over the bricks in order, then the coefficients
+      if (!last) return;
+      // gn_bwd_parts_finalize: per (n, c) fp64 sums over the bricks in order, then the coefficients
       double* const cs = reinterpret_cast<double*>(smem);  // [n * cout][2] (<= 8192 doubles: host-checked)
       lastarriver_rowsum<SC_NT>(g.gbparts, g.n, nbr, 2 * g.cout, cs);
       __syncthreads();
-      const int gcpg = g.cout / g.gbgroups;
-      const double M = (double)g.d * g.h * g.w * gcpg;
-      for (int p = tid; p < g.n * g.cout; p += SC_NT) {
-        const int n2 = p / g.cout, c = p - n2 * g.cout, gr = c / gcpg;
-        double a = 0, bb = 0;
-        for (int k2 = 0; k2 < gcpg; ++k2) {
-          const int cc = gr * gcpg + k2;
-          a += (double)g.gbgamma[cc] * cs[2 * (n2 * g.cout + cc)];
-          bb += (double)g.gbgamma[cc] * cs[2 * (n2 * g.cout + cc) + 1];
-        }
-        const float ca = (float)(a / M), cb = (float)(bb / M);
-        const float mu = g.gbstat[(n2 * g.gbgroups + gr) * 2], rs = g.gbstat[(n2 * g.gbgroups + gr) * 2 + 1];
-        const float scv = rs * g.gbgamma[c];
-        float* oc = g.coef + (long long)n2 * 5 * g.cout;
-        oc[c] = scv;
-        oc[g.cout + c] = g.gbbeta[c] - mu * scv;
-        oc[2 * g.cout + c] = rs * g.gbgamma[c];
-        oc[3 * g.cout + c] = -rs * rs * cb;
-        oc[4 * g.cout + c] = -rs * ca + rs * rs * cb * mu;
-      }
-      for (int c = tid; c < g.cout; c += SC_NT) {
-        double tg = 0, tb = 0;
-        for (int n2 = 0; n2 < g.n; ++n2) {
-          tb += cs[2 * (n2 * g.cout + c)];
-          tg += cs[2 * (n2 * g.cout + c) + 1];
-        }
-        if (g.dgamma) g.dgamma[c] = (float)tg;
-        if (g.dbeta) g.dbeta[c] = (float)tb;
-      }
+      const double M = (double)g.d * g.h * g.w * (g.cout / g.gbgroups);
+      gn_bwd_coefs<SC_NT>(cs, g.n, g.cout, g.gbgroups, M, g.gbstat, g.gbgamma, g.gbbeta, g.coef, g.dgamma, g.dbeta, 0);
       ts.mark<7>();
       return;
     }
@@ -485,30 +443,16 @@ __global__ __launch_bounds__(SC_NT, 512 / SC_NT) void conv_small_kernel(const bf
       __hip_atomic_store(g.spart + ((long long)nn * nbr + brick) * 32 + gr * 2 + (tid & 1), t2, __ATOMIC_RELAXED,
                          __HIP_MEMORY_SCOPE_AGENT);  // sc1
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
     ts.mark<5>();
-    const int ntiles = (int)(gridDim.x / g.nks);
-    if (tid == 0) {
-      const unsigned old = __hip_atomic_fetch_add(g.cnt + ntiles, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      s_last = old == (unsigned)(ntiles - 1);
-      if (s_last) __hip_atomic_store(g.cnt + ntiles, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
+    const bool last = last_arriver(g.cnt + ntiles, (unsigned)ntiles);
     ts.mark<6>();
     store_y();
-    if (!s_last) return;
+    if (!last) return;
     double* const cs = reinterpret_cast<double*>(smem) + 64;  // [n * 16][2] (past the wave rows in `red`)
     lastarriver_rowsum<SC_NT>(g.spart, g.n, nbr, 32, cs);
     __syncthreads();
-    for (int p = tid; p < g.n * 16; p += SC_NT) {
-      const double m = (double)g.cpg * g.d * g.h * g.w;
-      const double mean = cs[2 * p] / m;
-      double var = cs[2 * p + 1] / m - mean * mean;
-      if (var < 0) var = 0;
-      g.stats[p * 2] = (float)mean;
-      g.stats[p * 2 + 1] = (float)(1.0 / sqrt(var + 1e-5));
-    }
+    const double m = (double)g.cpg * g.d * g.h * g.w;
+    for (int p = tid; p < g.n * 16; p += SC_NT) gn_store_stats(g.stats + p * 2, cs[2 * p], cs[2 * p + 1], m);
     ts.mark<7>();
     return;
   }

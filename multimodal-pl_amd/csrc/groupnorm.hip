@@ -195,25 +195,8 @@ __device__ __forceinline__ void block_channel_reduce(float (&acc)[NV][VEC], floa
   }
 }
 
-// True (in every thread) for the block that finished last. Hand-off without fences (MI355X guide, inter-
-// workgroup visibility): partials are written with sc1 (write-through) stores, every wave drains them
-// (vmcnt(0)) before the barrier, one lane per block adds to the counter (agent scope), and the last block
-// reads the partials with sc1 loads (L2-served, not a stale L1).
-__device__ __forceinline__ bool block_is_last(unsigned* cnt, unsigned total) {
-  __shared__ unsigned s_last;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) s_last = atomicAdd(cnt, 1u) == total - 1;
-  __syncthreads();
-  if (s_last && threadIdx.x == 0) atomicExch(cnt, 0u);  // ready for the next launch
-  return s_last;
-}
-
-__device__ __forceinline__ float ld_sc1(const float* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// Last-block combine, phase 1: cs[p] = (sum_b P[n][b][0][c], sum_b P[n][b][1][c]) in fp64 for p = n*C + c.
+// Last-block combine (the block for which last_arriver, common.h, returned true), phase 1:
+// cs[p] = (sum_b P[n][b][0][c], sum_b P[n][b][1][c]) in fp64 for p = n*C + c.
 // Threads run along channels (coalesced partial rows) and over block slices; slices combine in fixed order.
 __device__ __forceinline__ void combine_channels(const float* __restrict__ ws, const RedGeom& g, double (*cs)[2],
                                                  int nv = 2, int k0 = 0) {
@@ -292,7 +275,7 @@ __global__ __launch_bounds__(GT) void gn_stats_kernel(const T* __restrict__ x, R
     }
   }
   block_channel_reduce<VEC, 2>(acc, lds, g, ws + ((long long)n * g.nblk + blk) * 2 * g.c);
-  if (!block_is_last(cnt, (unsigned)(g.n * g.nblk))) return;
+  if (!last_arriver(cnt, (unsigned)(g.n * g.nblk))) return;
   // combine: per (n, c) sums over the blocks, then per (n, group) over its channels, fixed order, fp64
   __shared__ double cs[GN_PAIRS_MAX][2];
   // the first group's shift is loaded before the combine (its latency overlaps the partial loads)
@@ -307,57 +290,15 @@ __global__ __launch_bounds__(GT) void gn_stats_kernel(const T* __restrict__ x, R
     }
     const double M = (double)g.v * g.cpg;
     const double shift = p == tid ? sh0 : to_f(x[(long long)nn * g.v * g.c + gr * g.cpg]);
-    const double dm = s1 / M;
-    double var = s2 / M - dm * dm;
-    if (var < 0) var = 0;
-    stats[(nn * g.groups + gr) * 2] = (float)(shift + dm);
-    stats[(nn * g.groups + gr) * 2 + 1] = (float)(1.0 / sqrt(var + 1e-5));
-  }
-}
-
-// (2) apply coefficients per (n, c) from the per-(n, c) sums cs; (3) dgamma / dbeta per c (gn_bwd_partial's last
-// block and gn_bwd_parts_finalize)
-__device__ __forceinline__ void gn_bwd_coefs(const double (*cs)[2], const RedGeom& g, const float* __restrict__ stats,
-                                             const float* __restrict__ gamma, const float* __restrict__ beta,
-                                             float* __restrict__ coef, float* __restrict__ dgamma,
-                                             float* __restrict__ dbeta, int accp) {
-  const int tid = threadIdx.x, npairs = g.n * g.c;
-  const double M = (double)g.v * g.cpg;
-  for (int p = tid; p < npairs; p += GT) {
-    const int nn = p / g.c, c = p % g.c, gr = c / g.cpg;
-    double a = 0, bb = 0;
-    for (int k = 0; k < g.cpg; ++k) {
-      const int cc = gr * g.cpg + k;
-      a += (double)gamma[cc] * cs[nn * g.c + cc][0];
-      bb += (double)gamma[cc] * cs[nn * g.c + cc][1];
-    }
-    const float ca = (float)(a / M), cb = (float)(bb / M);
-    const float mu = stats[(nn * g.groups + gr) * 2], rs = stats[(nn * g.groups + gr) * 2 + 1];
-    const float scv = rs * gamma[c];
-    float* o = coef + (long long)nn * 5 * g.c;
-    o[c] = scv;
-    o[g.c + c] = beta[c] - mu * scv;
-    o[2 * g.c + c] = rs * gamma[c];
-    o[3 * g.c + c] = -rs * rs * cb;
-    o[4 * g.c + c] = -rs * ca + rs * rs * cb * mu;
-  }
-  for (int c = tid; c < g.c; c += GT) {
-    double tg = 0, tb = 0;
-    for (int nn = 0; nn < g.n; ++nn) {
-      tb += cs[nn * g.c + c][0];
-      tg += cs[nn * g.c + c][1];
-    }
-    if (dgamma) dgamma[c] = (accp ? dgamma[c] : 0.f) + (float)tg;
-    if (dbeta) dbeta[c] = (accp ? dbeta[c] : 0.f) + (float)tb;
+    const GnStat st = gn_mean_rstd(s1, s2, M);  // of the shifted values: the variance is the same, the mean moves back
+    stats[(nn * g.groups + gr) * 2] = (float)(shift + st.mean);
+    stats[(nn * g.groups + gr) * 2 + 1] = st.rstd;
   }
 }
 
 // backward: per channel s1 = sum g, s2 = sum g*xhat (g = m*dA, m = the forward prologue's relu test
-// x*sc + sh > 0), then in the last block the apply coefficients of every (n, c), SoA coef[n][5][C]:
-//   sc, sh, alpha = rs*gamma_c, bx = -rs^2 * b_g, d = -rs*a_g + rs^2*b_g*mu
-// with a_g = sum_{c in g} gamma_c s1_c / M, b_g = sum gamma_c s2_c / M, so that
-//   dx = alpha * m * dA + bx * x + d  ==  rs * (gamma*m*dA - a_g - xhat * b_g)   (autograd of GN, unet3D.py:44-53)
-// and dgamma_c = sum_n s2, dbeta_c = sum_n s1.
+// x*sc + sh > 0), then in the last block the apply coefficients of every (n, c) and dgamma / dbeta (gn_bwd_coefs,
+// common.h), so that dx = alpha * m * dA + bx * x + d.
 template <typename T>
 __global__ __launch_bounds__(GT) void gn_bwd_partial(const T* __restrict__ da, const T* __restrict__ x, RedGeom g,
                                                     const float* __restrict__ stats, const float* __restrict__ gamma,
@@ -410,10 +351,10 @@ __global__ __launch_bounds__(GT) void gn_bwd_partial(const T* __restrict__ da, c
     }
   }
   block_channel_reduce<VEC, 2>(acc, lds, g, ws + ((long long)n * g.nblk + blk) * 2 * g.c);
-  if (!block_is_last(cnt, (unsigned)(g.n * g.nblk))) return;
+  if (!last_arriver(cnt, (unsigned)(g.n * g.nblk))) return;
   // (1) per (n, c): fp64 sums over the blocks, fixed order
   combine_channels(ws, g, cs);
-  gn_bwd_coefs(cs, g, stats, gamma, beta, coef, dgamma, dbeta, accp);
+  gn_bwd_coefs<GT>(&cs[0][0], g.n, g.c, g.groups, (double)g.v * g.cpg, stats, gamma, beta, coef, dgamma, dbeta, accp);
 }
 
 // The same backward when its per-channel partials come from the data-gradient ring's epilogue
@@ -473,7 +414,8 @@ __global__ __launch_bounds__(GPF) void gn_bwd_parts_finalize(const float* __rest
     }
     __syncthreads();
   }
-  if (tid < GT) gn_bwd_coefs(cs, g, stats, gamma, beta, coef, dgamma, dbeta, accp);  // (GT-strided loops)
+  if (tid < GT)  // (GT-strided loops)
+    gn_bwd_coefs<GT>(&cs[0][0], g.n, g.c, g.groups, (double)g.v * g.cpg, stats, gamma, beta, coef, dgamma, dbeta, accp);
 }
 
 // dx (+)= alpha*m*dA + bx*x + d per element; grid (blocks, n): a thread's 16-B channel chunk is fixed (the
@@ -616,42 +558,12 @@ __global__ __launch_bounds__(GT) void gn_bwd2_partial(const T* __restrict__ da1,
     }
   }
   block_channel_reduce<VEC, 4>(acc, lds, g, ws + ((long long)n * g.nblk + blk) * 4 * g.c);
-  if (!block_is_last(cnt, (unsigned)(g.n * g.nblk))) return;
-  const int npairs = g.n * g.c;
+  if (!last_arriver(cnt, (unsigned)(g.n * g.nblk))) return;
   const double M = (double)g.v * g.cpg;
   for (int k = 0; k < 2; ++k) {
-    const float* gamma = k ? gamma2 : gamma1;
-    const float* beta = k ? beta2 : beta1;
     combine_channels(ws, g, cs, 4, 2 * k);
-    for (int p = tid; p < npairs; p += GT) {
-      const int nn = p / g.c, c = p % g.c, gr = c / g.cpg;
-      double a = 0, bb = 0;
-      for (int q = 0; q < g.cpg; ++q) {
-        const int cc = gr * g.cpg + q;
-        a += (double)gamma[cc] * cs[nn * g.c + cc][0];
-        bb += (double)gamma[cc] * cs[nn * g.c + cc][1];
-      }
-      const float ca = (float)(a / M), cb = (float)(bb / M);
-      const float mu = stats[(nn * g.groups + gr) * 2], rs = stats[(nn * g.groups + gr) * 2 + 1];
-      const float scv = rs * gamma[c];
-      float* o = coef + ((long long)k * g.n + nn) * 5 * g.c;
-      o[c] = scv;
-      o[g.c + c] = beta[c] - mu * scv;
-      o[2 * g.c + c] = rs * gamma[c];
-      o[3 * g.c + c] = -rs * rs * cb;
-      o[4 * g.c + c] = -rs * ca + rs * rs * cb * mu;
-    }
-    float* dg = k ? dgamma2 : dgamma1;
-    float* db = k ? dbeta2 : dbeta1;
-    for (int c = tid; c < g.c; c += GT) {
-      double tg = 0, tb = 0;
-      for (int nn = 0; nn < g.n; ++nn) {
-        tb += cs[nn * g.c + c][0];
-        tg += cs[nn * g.c + c][1];
-      }
-      if (dg) dg[c] = (accp ? dg[c] : 0.f) + (float)tg;
-      if (db) db[c] = (accp ? db[c] : 0.f) + (float)tb;
-    }
+    gn_bwd_coefs<GT>(&cs[0][0], g.n, g.c, g.groups, M, stats, k ? gamma2 : gamma1, k ? beta2 : beta1,
+                     coef + (long long)k * g.n * 5 * g.c, k ? dgamma2 : dgamma1, k ? dbeta2 : dbeta1, accp);
     __syncthreads();  // cs is rebuilt for the second set
   }
 }

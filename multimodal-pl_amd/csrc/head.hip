@@ -514,17 +514,8 @@ __global__ __launch_bounds__(HD_T) void head_loss_bwd_kernel(const float* __rest
     // round 6: the bias gradient summed by the launch's last-arriving block (fixed row order, fp64) instead of two
     // channel-sum launches after it; the counter is left zeroed
     if (dbias == nullptr) return;
-    __shared__ unsigned s_last;
     __shared__ double cs[16];
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const unsigned old = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      s_last = old == gridDim.x - 1;
-      if (s_last) __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    if (!s_last) return;
+    if (!last_arriver(cnt, gridDim.x)) return;
     lastarriver_rowsum<HD_T>(dbp, 1, (int)gridDim.x, cout, cs);
     __syncthreads();
     if (threadIdx.x < cout) dbias[threadIdx.x] = (float)cs[threadIdx.x];

@@ -102,8 +102,9 @@ if small:  # the tail after the main loop (TailStamps: slab stores, their drain,
     assert h.u3d_diag_small_tail(ctypes.c_void_p(tb.ctypes.data), ctypes.c_longlong(tb.nbytes)) == 0
     t = tb.reshape(1024, 16)[:nwg].astype(np.float64)
     mhz = np.median(clk)
-    segs = ("slab stores issued", "stores drained", "tile counter", "combine", "partials stored", "stats counter",
-            "finalize")
+    # (marks 2 and 5 sit in front of last_arriver: its drain and barriers count with the counter segment after them)
+    segs = ("slab stores issued", "to the tile hand-off", "drain + tile counter", "combine", "partials issued",
+            "drain + stats counter", "finalize")
     for lab, sel in (("all", t[:, 3] > 0), ("tile-last", t[:, 4] > 0), ("final", t[:, 7] > 0)):
         q = t[sel]
         if not len(q):
