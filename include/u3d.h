@@ -68,7 +68,8 @@ typedef struct u3d_wstd_desc {
 } u3d_wstd_desc;
 /* Fused SGD step over up to U3D_SGD_BATCH_MAX fp32 tensors (torch.optim.SGD semantics: d = g (+ wd*p),
  * buf = momentum*buf + (1-dampening)*d (buf = d when init), d = nesterov ? d + momentum*buf : buf, p -= lr*d;
- * maximize negates g). lr is read from device memory (graph-capturable LR changes). Reference: the SGD of
+ * maximize negates g). lr is read from device memory (graph-capturable LR changes). A descriptor with n == 0 may
+ * carry null pointers (a zero-element tensor has no storage) and is skipped. Reference: the SGD of
  * train_amos_atlas_final.py:132-135,378. */
 typedef struct {
   float* p;

@@ -71,8 +71,10 @@ extern "C" int u3d_sgd_step(const u3d_sgd_desc* descs, int count, const float* l
   SgdBatch bt{};
   long long blocks = 0;
   for (int i = 0; i < count; ++i) {
-    U3D_REQUIRE(descs[i].p && descs[i].g && descs[i].n >= 0, "sgd_step: bad descriptor %d", i);
-    U3D_REQUIRE(momentum == 0.f || descs[i].buf, "sgd_step: descriptor %d needs a momentum buffer", i);
+    // a zero-element tensor has no storage (torch hands out null pointers) and gets no block
+    U3D_REQUIRE(descs[i].n >= 0 && (descs[i].n == 0 || (descs[i].p && descs[i].g)), "sgd_step: bad descriptor %d", i);
+    U3D_REQUIRE(momentum == 0.f || descs[i].n == 0 || descs[i].buf, "sgd_step: descriptor %d needs a momentum buffer",
+                i);
     bt.d[bt.count] = descs[i];
     bt.b0[bt.count++] = blocks;
     blocks += (descs[i].n + SG_PER - 1) / SG_PER;
