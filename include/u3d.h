@@ -450,6 +450,26 @@ int u3d_partial_loss_bwd(int dtype_out, const float* logits, const float* labels
                          int softmax, const float* weights, int uce, const double* sums, const float* grad_out,
                          void* dlogits, u3d_stream_t stream);
 
+/* ---------------------------------------------------------------- deep-supervision loss (get_loss's deep_out branch)
+ * Reference losses.py:119-129: loss = sum_l level_weights[l] * EDiceLoss_partial(C)(logits_l, nearest(target, size_l),
+ * soft_max=True, mask=[w], uce=False) over L <= 4 decoder levels, one launch over all levels plus a one-workgroup
+ * finalize (forward) and one launch (backward). The F.interpolate(target, size_l, mode='nearest') of :123 is not
+ * materialised: each level voxel reads the full-resolution target at min((int)floorf(i * (float)in / out), in - 1)
+ * per axis, torch's CPU nearest index. logits / dlogits: HOST arrays of L device pointers, fp32 NDHWC
+ * [S][d_l][h_l][w_l][C]; dims: host int [L][3] = (d_l, h_l, w_l); level_weights: host float [L] (:116); target fp32
+ * [S][D][H][W] (integer-valued); weights fp32 [C] (= mask[0][:C]). The host arrays are read during the call only:
+ * pointers and extents travel in the kernel arguments, so the calls can be captured in a graph.
+ * sums fp64 [L][C][4] = per level and class (sum p*t, sum p^2, sum t, 0) over the whole batch; level_loss fp32 [L];
+ * loss fp32 [1]. ws: u3d_deepsup_loss_workspace_bytes(L, C) bytes. Fewer than 2^26 voxels per level. */
+long long u3d_deepsup_loss_workspace_bytes(int L, int C);
+int u3d_deepsup_loss_fwd(int L, const float* const* logits, const int* dims, const float* level_weights,
+                         const float* target, int S, int D, int H, int W, int C, const float* weights, double* sums,
+                         float* level_loss, float* loss, float* ws, u3d_stream_t stream);
+/* dlogits[l] = d loss / d logits_l * grad_out[0] (device scalar), from the forward's sums */
+int u3d_deepsup_loss_bwd(int L, const float* const* logits, const int* dims, const float* level_weights,
+                         const float* target, int S, int D, int H, int W, int C, const float* weights,
+                         const double* sums, const float* grad_out, float* const* dlogits, u3d_stream_t stream);
+
 /* Partial-label target (A12, train_amos_atlas_final.py:252-255): out = labels with every label l in [lmin, lmax]
  * whose mask[s][l] == 0 set to 0; mask int64 [S][mask_stride] (mask_stride 0 = one vector for the batch), length M. */
 int u3d_partial_target(const float* labels, int S, long long V, const long long* mask, int mask_stride, int M,

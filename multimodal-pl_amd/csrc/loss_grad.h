@@ -4,7 +4,51 @@
 #pragma once
 #include "common.h"
 
+// dispatch on the class count: exact instantiations for the model heads, a guarded 32-wide fallback
+#define U3D_NC_DISPATCH(C, F)        \
+  switch (C) {                       \
+    case 2: F(2); break;             \
+    case 8: F(8); break;             \
+    case 14: F(14); break;           \
+    case 16: F(16); break;           \
+    default: F(32); break;           \
+  }
+
 namespace u3d {
+
+constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
+
+// Softmax path on the hardware transcendentals (v_exp_f32 / v_log_f32 / v_rcp_f32, ~1 ulp): e_c = 2^((x_c-m)
+// log2 e), p_c = e_c / s, and the two logs BCE needs are exact identities of the softmax instead of log(p):
+//   log p_c = (x_c - m) - ln s,   log(1 - p_c) = ln(s - e_c) - ln s.
+// The loss was transcendental-bound with libm expf/logf/log1pf (48 calls per voxel at C = 16).
+// Shared by loss.hip and deepsup.hip (the deep-supervision levels take the same softmax).
+template <int NC>
+__device__ __forceinline__ void softmax_fast(const float* __restrict__ lg, int C, float (&x)[NC], float (&e)[NC],
+                                             float& s, float& inv) {
+  if constexpr (NC % 4 == 0 && NC <= 16) {
+#pragma unroll
+    for (int c = 0; c < NC; c += 4) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(lg + c);
+      x[c] = v[0]; x[c + 1] = v[1]; x[c + 2] = v[2]; x[c + 3] = v[3];
+    }
+  } else {
+#pragma unroll
+    for (int c = 0; c < NC; ++c) x[c] = c < C ? lg[c] : 0.f;
+  }
+  float m = -INFINITY;
+#pragma unroll
+  for (int c = 0; c < NC; ++c)
+    if (c < C) m = fmaxf(m, x[c]);
+  s = 0.f;
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    x[c] -= m;
+    e[c] = c < C ? __builtin_amdgcn_exp2f(x[c] * LOG2E) : 0.f;
+    s += e[c];
+  }
+  inv = __builtin_amdgcn_rcpf(s);
+}
 
 // per-class coefficients: dL/dp_c = t_c * a + p_c * b (+ the BCE term e * (p_c - t_c) / ((1 - p_c) p_c))
 //   d(1 - num/den)/dp = -(2 t den - num * 2 p) / den^2, num = 2 I + 1e-5, den = Z + Y + 1e-5 (per class sums)

@@ -1,6 +1,6 @@
 """Drop-in for the reference loss_functions/losses.py: get_loss — the pre-train branch (losses.py:107-113,
 179-182, train_amos_atlas_final.py:303-304) and the refiner-consistency branch over the feam3 attention maps
-(:131-178, train_amos_atlas_final.py:312) — and the refiner loss get_loss_refine (:46-62)."""
+(:131-178, train_amos_atlas_final.py:312), with the deep-supervision term of ``deep_out`` (:119-129) — and the refiner loss get_loss_refine (:46-62)."""
 import torch
 import torch.nn.functional as F
 from torch.nn.modules.loss import _WeightedLoss
@@ -14,18 +14,27 @@ def get_loss(output, cm, deep_out, target, mask=None, catlas=None, attns=None, r
     consistency term: masked soft Dice of every attention map (sigmoid) and of softmax(output)[:, 1:] against the
     refiner's confident foreground for the organs label_t marks unsupervised (u3d.loss.consistency_aux, one fused
     pass). ``refine_label`` (:134-157) is never read by the reference and is not built; ``refine_output`` carries
-    no gradient (the driver computes it under no_grad, train_amos_atlas_final.py:285-287). Returns (loss, 0.10)."""
-    if len(deep_out) != 0:
-        raise NotImplementedError("get_loss: the deep_out branch (losses.py:119-129) is never used by the driver "
-                                  "(train_amos_atlas_final.py:304, 312 pass []) and is not built")
+    no gradient (the driver computes it under no_grad, train_amos_atlas_final.py:285-287). Returns (loss, 0.10).
+
+    ``deep_out`` (:119-129): the deep-supervision maps of unet3D_with_deepsup / _feam3 / _feam2, each scored by the
+    soft Dice alone (uce=False) against the nearest-resized target, weighted 0.125, 0.25, 0.5, 1
+    (u3d.loss.deep_supervision_loss, one fused pass over all levels). As in the reference the term joins the
+    consistency branch only: the pre-train branch returns ``dice_loss`` and drops it (:179-182), so the deep maps get
+    no gradient there and nothing is computed for them. More than four levels raise IndexError, a level with another
+    class count or batch AssertionError. The per-level ``.detach().cpu()`` (:127) is dropped (no host sync)."""
+    from u3d import loss as L
+    deep_out = list(deep_out)
+    if deep_out:
+        L.check_deep_levels(deep_out, target, output.shape[1])
     edice = EDiceLoss_partial(output.shape[1])
     dice_loss = edice(output, target.squeeze(1), soft_max=True, mask=mask)
     if refine_output is None:
         return dice_loss, confi_
-    from u3d import loss as L
     if not torch.is_tensor(label_t):
         label_t = torch.tensor(label_t, dtype=torch.float32)
     aux = L.consistency_aux(output, list(attns), refine_output, label_t, weight_feature, confi=0.10)
+    if deep_out:
+        aux = L.deep_supervision_loss(deep_out, target, mask) + aux
     return dice_loss + aux * aux_weight, 0.10
 
 

@@ -105,9 +105,10 @@ def eam_op(tape, f, key, token, up):
     return out
 
 
-def _feam3_forward(tape, cfg, x, tokens, use_cm, deep_up, heads=True, renew=None):
+def _feam3_forward(tape, cfg, x, tokens, use_cm, deep_up, heads=True, renew=None, store=True):
     """renew = (mask, num_classes, alpha): unet3D_with_feam2's in-forward class-token update of each level, before
-    that level's attention (unet3D.py:869-878, 896-903, 919-926)."""
+    that level's attention (unet3D.py:869-878, 896-903, 919-926). store=False: no detached feature copies
+    (unet3D_with_deepsup, unet3D.py:370-429: the trunk and the three deep-supervision heads alone)."""
     f, _ = tape.trunk(x, cfg)
     lg = tape.head(f, cfg)
     att, deep, feats = [], [], []
@@ -116,7 +117,8 @@ def _feam3_forward(tape, cfg, x, tokens, use_cm, deep_up, heads=True, renew=None
             fk = tape.dec[k]
             deep.append(tape.gn_conv(fk, f"deepout{k + 1}.2", 1, 1, gn_key=f"deepout{k + 1}.0", G=16, bias=True,
                                      out_f32=True, standardize=False))
-            feats.append(fk.t.detach().clone())
+            if store:
+                feats.append(fk.t.detach().clone())
             if renew is not None:
                 renew_token([tokens[k]], [fk.t.permute(0, 4, 1, 2, 3)], renew[0], renew[1], renew[2])
             if use_cm[k]:
@@ -130,14 +132,14 @@ def _ncdhw(t):
 
 class _Feam3Fn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, cfg, dtype, use_cm, deep_up, names, x, tokens, *tensors):
+    def forward(ctx, cfg, dtype, use_cm, deep_up, store, names, x, tokens, *tensors):
         ctx.set_materialize_grads(False)
         P = dict(zip(names, tensors))
         tape = trunk.Tape(P, dtype, record=True)
         tape.sink = current_sink()
         if tape.sink is not None:
             tape.sink.begin()
-        lg, att, deep, feats = _feam3_forward(tape, cfg, x, tokens, use_cm, deep_up)
+        lg, att, deep, feats = _feam3_forward(tape, cfg, x, tokens, use_cm, deep_up, store=store)
         ctx.state = (tape, lg, att, deep)
         ctx.names = names
         ctx.n_att = len(att)
@@ -165,36 +167,38 @@ class _Feam3Fn(torch.autograd.Function):
         if tape.sink is not None:
             pg = tape.sink.returned(ctx.names, pg)
         ctx.state = None
-        return (None, None, None, None, None, None, None, *pg)
+        return (None, None, None, None, None, None, None, None, *pg)
 
 
-def run_feam3(model, x, renew=None):
+def run_feam3(model, x, renew=None, eam=True):
     """model: unet3D.unet3D_with_feam3 (or _feam2). Returns train: (logits, atten_map, deep_map, feature_stored);
-    eval: logits."""
+    eval: logits. eam=False: unet3D.unet3D_with_deepsup, the same graph without the EAMs, the class tokens and the
+    stored features (atten_map and feature_stored come back empty; any batch size)."""
     ops.require_device(x)
     cfg = model._u3d_cfg
     dtype = trunk.compute_dtype(getattr(model, "compute_dtype", None))
     x = x.float().contiguous()
-    tokens = [model.class_token1, model.class_token2, model.class_token3]
-    use_cm = tuple(bool(u) for u in model.use_cm)
+    tokens = [model.class_token1, model.class_token2, model.class_token3] if eam else None
+    use_cm = tuple(bool(u) and eam for u in model.use_cm)
+    deep_up = bool(eam and model.deep_up)
     named = list(model.named_parameters())
     if not model.training:
         with torch.no_grad():
             tape = trunk.Tape(dict(named), dtype, record=False)
-            lg, _, _, _ = _feam3_forward(tape, cfg, x, tokens, use_cm, model.deep_up, heads=False)
+            lg, _, _, _ = _feam3_forward(tape, cfg, x, tokens, use_cm, deep_up, heads=False)
         return _ncdhw(lg.t)
     if torch.is_grad_enabled() and any(p.requires_grad for _, p in named):
         if renew is not None:
             raise RuntimeError("a leaf Variable that requires grad is being used in an in-place operation.")
-        outs = _Feam3Fn.apply(cfg, dtype, use_cm, bool(model.deep_up), [nm for nm, _ in named], x, tokens,
+        outs = _Feam3Fn.apply(cfg, dtype, use_cm, deep_up, eam, [nm for nm, _ in named], x, tokens,
                               *[p for _, p in named])
     else:
         with torch.no_grad():
             tape = trunk.Tape(dict(named), dtype, record=False)
-            lg, att, deep, feats = _feam3_forward(tape, cfg, x, tokens, use_cm, model.deep_up, renew=renew)
+            lg, att, deep, feats = _feam3_forward(tape, cfg, x, tokens, use_cm, deep_up, renew=renew, store=eam)
         outs = [_ncdhw(lg.t)] + [a.t for a in att] + [_ncdhw(d.t) for d in deep] + [_ncdhw(ft) for ft in feats]
     na = sum(use_cm)
-    return outs[0], list(outs[1:1 + na]), list(outs[1 + na:4 + na]), list(outs[4 + na:7 + na])
+    return outs[0], list(outs[1:1 + na]), list(outs[1 + na:4 + na]), list(outs[4 + na:])
 
 
 def renew_token(tokens, features, mask, num_classes, alpha):

@@ -1,4 +1,6 @@
 """Autograd Function for the fused partial-label Dice + BCE loss (reference loss_partial.py:59-99)."""
+import ctypes
+
 import torch
 from torch.utils import _pytree as pytree
 
@@ -94,6 +96,86 @@ def partial_loss(logits, target, weights, mode=MODE_SOFTMAX, uce=True):
     if target.shape[0] != logits.shape[0] or target.numel() * logits.shape[1] != logits.numel():
         raise AssertionError(f"predict {tuple(logits.shape)} & target {tuple(target.shape)} shape do not match")
     return _PartialLossFn.apply(logits, target, weights, mode, uce)
+
+
+# ------------------------------------------------------------------ deep supervision (losses.py:119-129)
+DEEP_WEIGHTS = (0.125, 0.25, 0.5, 1.0)   # losses.py:116
+DEEPSUP_SLOT = 10
+
+
+def _deepsup_host_args(lgs, level_weights):
+    """The per-level host arrays of u3d_deepsup_loss_fwd/_bwd (read during the call only)."""
+    L = len(lgs)
+    ptrs = (ctypes.c_void_p * L)(*[t.data_ptr() for t in lgs])
+    dims = (ctypes.c_int * (3 * L))(*[int(n) for t in lgs for n in t.shape[1:4]])
+    lw = (ctypes.c_float * L)(*[float(w) for w in level_weights])
+    return ptrs, dims, lw
+
+
+class _DeepSupFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, target, weights, level_weights, *deep):
+        lgs = [ndhwc_view(l.float()) for l in deep]
+        tgt = target.float().contiguous()
+        L, (S, C) = len(lgs), (lgs[0].shape[0], lgs[0].shape[-1])
+        D, H, W = tgt.shape[-3:]
+        dev = tgt.device
+        sums = torch.empty((L, C, 4), dtype=torch.float64, device=dev)
+        level_loss = torch.empty(L, dtype=torch.float32, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        ws = ops.WS.get(_lib_query("u3d_deepsup_loss_workspace_bytes", L, C), dev, slot=DEEPSUP_SLOT)
+        ptrs, dims, lw = _deepsup_host_args(lgs, level_weights)
+        ops.call("u3d_deepsup_loss_fwd", L, ptrs, dims, lw, tgt.data_ptr(), S, D, H, W, C, weights.data_ptr(),
+                 sums.data_ptr(), level_loss.data_ptr(), loss.data_ptr(), ws.data_ptr(), ops._stream())
+        ctx.save_for_backward(tgt, weights, sums, *lgs)
+        ctx.level_weights = tuple(level_weights)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        tgt, weights, sums, *lgs = ctx.saved_tensors
+        L, (S, C) = len(lgs), (lgs[0].shape[0], lgs[0].shape[-1])
+        D, H, W = tgt.shape[-3:]
+        go = g.reshape(1).float().contiguous()
+        dls = [torch.empty_like(t) for t in lgs]
+        ptrs, dims, lw = _deepsup_host_args(lgs, ctx.level_weights)
+        dptrs = (ctypes.c_void_p * L)(*[t.data_ptr() for t in dls])
+        ops.call("u3d_deepsup_loss_bwd", L, ptrs, dims, lw, tgt.data_ptr(), S, D, H, W, C, weights.data_ptr(),
+                 sums.data_ptr(), go.data_ptr(), dptrs, ops._stream())
+        # NCDHW-shaped views over NDHWC storage: what the native heads' backward takes without a copy
+        return (None, None, None, *[d.permute(0, 4, 1, 2, 3) for d in dls])
+
+
+def deep_supervision_loss(deep_out, target, mask=None, level_weights=DEEP_WEIGHTS):
+    """get_loss's deep-supervision term (losses.py:119-129): sum over the levels of level_weights[idx] *
+    EDiceLoss_partial(C)(l, F.interpolate(target, l.shape[2:], mode='nearest').squeeze(1), soft_max=True, mask=mask,
+    uce=False), as one fused multi-level pass each way (u3d_deepsup_loss_fwd/_bwd; the resized targets are never
+    built). deep_out: [S, C, d, h, w] logits per level (NCDHW views of NDHWC storage, as the native heads return, are
+    read in place; plain NCDHW costs one copy); target [S, 1, D, H, W] (or [S, D, H, W]). More levels than weights
+    raise IndexError (weights[idx]), a level with another C or batch AssertionError, as the reference."""
+    deep_out = list(deep_out)
+    if len(deep_out) == 0:
+        raise ValueError("deep_supervision_loss: no levels")
+    C = deep_out[0].shape[1]
+    check_deep_levels(deep_out, target, C, len(level_weights))
+    ops.require_device(target, *deep_out)
+    w = class_weights(mask, C, target.device)
+    return _DeepSupFn.apply(target[:, 0] if target.dim() == 5 else target, w,
+                            tuple(float(x) for x in level_weights[:len(deep_out)]), *deep_out)
+
+
+def check_deep_levels(deep_out, target, C, n_weights=len(DEEP_WEIGHTS)):
+    """The failures of the reference's loop over the levels (losses.py:121-129), in its order: a level past the
+    weights list is an IndexError (weights[idx]); a level whose class count or batch differs from the one-hot
+    target's is DiceLoss's AssertionError (loss_partial.py:46)."""
+    if target.dim() not in (4, 5) or (target.dim() == 5 and target.shape[1] != 1):
+        raise AssertionError(f"target {tuple(target.shape)}: [S, 1, D, H, W] labels expected")
+    for idx, l in enumerate(deep_out):
+        if l.dim() != 5 or l.shape[0] != target.shape[0] or l.shape[1] != C:
+            raise AssertionError(f"predict {tuple(l.shape)} & target {(target.shape[0], C) + tuple(l.shape[2:])} "
+                                 "shape do not match")
+        if idx >= n_weights:
+            raise IndexError("list index out of range")
 
 
 # ------------------------------------------------------------------ consistency branch (losses.py:131-178)

@@ -246,6 +246,36 @@ class EAM(nn.Module):
                        "on the hot path")
 
 
+def _build_deep_trunk(self, layers, num_classes, eam):
+    """The modules unet3D_with_feam3 (:958-1014) and unet3D_with_deepsup (:288-341) share, in the reference's
+    registration order: the trunk with a deep-supervision head deepout{1,2,3} after x8 / x4 / x2_resb and, with
+    ``eam``, an EAM after each head (plus the x4 / x8 upsamplers of deep_up)."""
+    mk = lambda cin, cout, n, s: _make_layer(self, NoBottleneck, cin, cout, n, stride=s)  # noqa: E731
+    self.conv1 = conv3x3x3(1, 32, stride=[1, 1, 1], weight_std=self.weight_std)
+    self.layer0 = mk(32, 32, layers[0], (1, 1, 1))
+    self.layer1 = mk(32, 64, layers[1], (2, 2, 2))
+    self.layer2 = mk(64, 128, layers[2], (2, 2, 2))
+    self.layer3 = mk(128, 256, layers[3], (2, 2, 2))
+    self.layer4 = mk(256, 256, layers[4], (2, 2, 2))
+    self.fusionConv = nn.Sequential(
+        nn.GroupNorm(16, 256), nn.ReLU(inplace=in_place),
+        conv3x3x3(256, 256, kernel_size=(1, 1, 1), padding=(0, 0, 0), weight_std=self.weight_std))
+    self.upsamplex2 = nn.Upsample(scale_factor=2, mode="trilinear")
+    if eam:
+        self.upsamplex3 = nn.Upsample(scale_factor=4, mode="trilinear")
+        self.upsamplex4 = nn.Upsample(scale_factor=8, mode="trilinear")
+    head = lambda c: nn.Sequential(nn.GroupNorm(16, c), nn.ReLU(inplace=in_place),  # noqa: E731
+                                   nn.Conv3d(c, num_classes, kernel_size=1))
+    for k, (name, cin, cout, ekey) in enumerate((("x8_resb", 256, 128, "eam84"), ("x4_resb", 128, 64, "eam42"),
+                                                 ("x2_resb", 64, 32, "eam21"))):
+        setattr(self, name, mk(cin, cout, 1, (1, 1, 1)))
+        setattr(self, f"deepout{k + 1}", head(cout))
+        if eam:
+            setattr(self, ekey, EAM(cout, input_resolution=None, num_heads=4))
+    self.x1_resb = mk(32, 32, 1, (1, 1, 1))
+    self.precls_conv = head(32)
+
+
 class unet3D_with_feam3(_TrunkMixin, nn.Module):
     """Reference unet3D.py:938-1190 (the model train_amos_atlas_final.py:118 trains): the trunk + deep-supervision
     heads deepout1-3 + EAM attention maps against EMA class tokens. forward(input, mask=None) -> train:
@@ -261,32 +291,7 @@ class unet3D_with_feam3(_TrunkMixin, nn.Module):
         self.alpha = 0.01
         self.deep_up = deep_up
         super().__init__()
-        mk = lambda cin, cout, n, s: _make_layer(self, NoBottleneck, cin, cout, n, stride=s)  # noqa: E731
-        self.conv1 = conv3x3x3(1, 32, stride=[1, 1, 1], weight_std=self.weight_std)
-        self.layer0 = mk(32, 32, layers[0], (1, 1, 1))
-        self.layer1 = mk(32, 64, layers[1], (2, 2, 2))
-        self.layer2 = mk(64, 128, layers[2], (2, 2, 2))
-        self.layer3 = mk(128, 256, layers[3], (2, 2, 2))
-        self.layer4 = mk(256, 256, layers[4], (2, 2, 2))
-        self.fusionConv = nn.Sequential(
-            nn.GroupNorm(16, 256), nn.ReLU(inplace=in_place),
-            conv3x3x3(256, 256, kernel_size=(1, 1, 1), padding=(0, 0, 0), weight_std=self.weight_std))
-        self.upsamplex2 = nn.Upsample(scale_factor=2, mode="trilinear")
-        self.upsamplex3 = nn.Upsample(scale_factor=4, mode="trilinear")
-        self.upsamplex4 = nn.Upsample(scale_factor=8, mode="trilinear")
-        head = lambda c: nn.Sequential(nn.GroupNorm(16, c), nn.ReLU(inplace=in_place),  # noqa: E731
-                                       nn.Conv3d(c, num_classes, kernel_size=1))
-        self.x8_resb = mk(256, 128, 1, (1, 1, 1))
-        self.deepout1 = head(128)
-        self.eam84 = EAM(128, input_resolution=None, num_heads=4)
-        self.x4_resb = mk(128, 64, 1, (1, 1, 1))
-        self.deepout2 = head(64)
-        self.eam42 = EAM(64, input_resolution=None, num_heads=4)
-        self.x2_resb = mk(64, 32, 1, (1, 1, 1))
-        self.deepout3 = head(32)
-        self.eam21 = EAM(32, input_resolution=None, num_heads=4)
-        self.x1_resb = mk(32, 32, 1, (1, 1, 1))
-        self.precls_conv = head(32)
+        _build_deep_trunk(self, layers, num_classes, eam=True)
         # class tokens: plain tensors (not parameters / buffers, so not in the state_dict), :1016-1021
         self.class_token1 = torch.randn(num_classes - 1, 128)
         self.class_token2 = torch.randn(num_classes - 1, 64)
@@ -344,11 +349,36 @@ class unet3D_with_feam2(unet3D_with_feam3):
         return outs[0], outs[1], outs[2]
 
 
+class unet3D_with_deepsup(_TrunkMixin, nn.Module):
+    """Reference unet3D.py:280-429: the trunk + the three deep-supervision heads deepout1-3 (GN(16), ReLU, 1^3 conv +
+    bias on the x8 / x4 / x2 decoder features), no EAM and no class tokens. forward(input, ids) -> train: (logits,
+    [deep x8, deep x4, deep x2]); eval: logits (the heads are not run). ``ids`` is unused, as in the reference; any
+    batch size. The deep maps are trained by losses.get_loss(..., deep_out=...) / u3d.loss.deep_supervision_loss."""
+
+    def __init__(self, layers, num_classes=12, weight_std=False, ema=False, use_cm=[True, True, True]):  # noqa: B006
+        self.inplanes = 128
+        self.weight_std = weight_std
+        self.num_classes = num_classes
+        self.use_cm = use_cm
+        super().__init__()
+        _build_deep_trunk(self, layers, num_classes, eam=False)
+        self._u3d_cfg = trunk.TrunkCfg(layers=tuple(layers), weight_std=bool(self.weight_std))
+        if ema:
+            for param in self.parameters():
+                param.detach_()
+
+    def forward(self, input, ids=None):
+        from u3d import feam
+        outs = feam.run_feam3(self, input, eam=False)
+        if self.training:
+            return outs[0], outs[2]
+        return outs
+
+
 # Method-specific variants and discriminators (SURVEY.md §2 rows 3-4): next rows, not on the trunk path.
 unet3D_with_feam = _next_row("unet3D_with_feam", "f2")
 unet3D_with_eam = _next_row("unet3D_with_eam", "f2")
 unet3D_with_eam_baseline = _next_row("unet3D_with_eam_baseline", "f2")
-unet3D_with_deepsup = _next_row("unet3D_with_deepsup", "f2")
 get_style_discriminator = _next_row("get_style_discriminator", "out-of-scope")
 get_style_discriminator_output = _next_row("get_style_discriminator_output", "out-of-scope")
 deep_style_discriminator_output = _next_row("deep_style_discriminator_output", "out-of-scope")
