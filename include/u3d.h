@@ -164,6 +164,24 @@ int u3d_conv_small_dgrad_gn(const void* dy, int n, int cout, int d, int h, int w
                             const void* x, const float* gn_stats, const float* gn_gamma, const float* gn_beta,
                             int gn_groups, void* dx, float* ws, long long ws_bytes, unsigned* cnt, float* parts,
                             float* coef, float* dgamma, float* dbeta, int* made, u3d_stream_t stream);
+/* u3d_conv_small_dgrad_gn and the same conv's weight gradient (u3d_conv_wgrad_ring's 12 x 12-tile kernel or
+ * u3d_conv_wgrad_brick's 3 x 8 x 16 stride-1 kernel, GroupNorm + ReLU prologue on x = the GroupNorm whose backward the
+ * data gradient takes) as two sub-grids of ONE launch: data-gradient workgroups first, weight-gradient workgroups on the
+ * CUs they leave (no barrier between the halves). Every output is bitwise what the two separate entry points write:
+ * dx, coef, dgamma, dbeta as u3d_conv_small_dgrad_gn; partials[nsplit][27][cout_p][cin_p] with nsplit and slab layout
+ * of u3d_conv_wgrad_ring_splits (ring != 0) / u3d_conv_wgrad_brick_splits(stride 1) (ring == 0). `ring`: which of the
+ * two the caller routes this conv's weight gradient to. u3d_conv_small_bwd_pair_ok returns that nsplit, or 0 where the
+ * pair does not run; u3d_conv_small_bwd_pair then launches nothing and returns 0 with *made = 0 (the caller takes the
+ * separate entry points): a data gradient that would not split its contraction 2..8 ways, n * cin * 2 > 8192, a weight
+ * gradient that is neither kernel above, operands / slabs beyond the 32-bit offset range. Workspaces as
+ * u3d_conv_small_dgrad_gn. Reference: autograd of NoBottleneck's relu(gn(x)) -> conv3x3x3 (unet3D.py:44-73): grad of
+ * F.conv3d (unet3D.py:27) w.r.t. its input and its weight. */
+int u3d_conv_small_bwd_pair_ok(int n, int cout, int d, int h, int w, int cin, int ring, long long ws_bytes);
+int u3d_conv_small_bwd_pair(const void* dy, int n, int cout, int d, int h, int w, const void* wpk_dgrad, int cin,
+                            const void* x, const float* gn_stats, const float* gn_gamma, const float* gn_beta,
+                            int gn_groups, void* dx, float* ws, long long ws_bytes, unsigned* cnt, float* parts,
+                            float* coef, float* dgamma, float* dbeta, int ring, float* partials, int nsplit,
+                            int* made, u3d_stream_t stream);
 /* the apply pass of the GroupNorm backward from precomputed coefficients coef[n][5][c] (bf16 dA, x, dx) */
 int u3d_gn_bwd_apply_coef(const void* da, const void* x, int n, int c, long long v, int groups, const float* coef,
                           void* dx, int accumulate, u3d_stream_t stream);

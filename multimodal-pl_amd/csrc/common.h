@@ -431,13 +431,18 @@ __device__ __forceinline__ double wave_sum(double v) {
 struct TileSplit {
   int tx, ty, split;
 };
-__device__ __forceinline__ TileSplit xcd_tile_split() {
-  const int nt = gridDim.x * gridDim.y, total = nt * gridDim.z;
-  const int L = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
+// The same for workgroup L of `total` = gx * gy * splits laid out linearly (x fastest): a sub-grid of a larger launch,
+// provided workgroups L and L + 8 share an XCD (the sub-grid starts at a multiple of 8 of the launch's linear index).
+__device__ __forceinline__ TileSplit xcd_tile_split(int L, int gx, int gy, int total) {
+  const int nt = gx * gy;
   const int q = total >> 3, rr = total & 7, xcd = L & 7, loc = L >> 3;
   const int N = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + loc;
   const int tile = N % nt;
-  return TileSplit{tile % (int)gridDim.x, tile / (int)gridDim.x, N / nt};
+  return TileSplit{tile % gx, tile / gx, N / nt};
+}
+__device__ __forceinline__ TileSplit xcd_tile_split() {
+  return xcd_tile_split(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z), gridDim.x, gridDim.y,
+                        gridDim.x * gridDim.y * gridDim.z);
 }
 
 __host__ __device__ inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }

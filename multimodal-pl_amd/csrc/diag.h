@@ -44,7 +44,7 @@ struct PhaseStamps {
   }
   __device__ __forceinline__ void end(unsigned long long* buf, int wg, int wave, int lane) {
     const unsigned long long t1 = stamp_clk(), r1 = stamp_real();
-    if (lane == 0) {
+    if (lane == 0 && buf) {  // (null: a kernel that keeps no stamps of this body)
       unsigned long long* o = buf + ((long long)wg * 8 + wave) * 8;
       o[0] = t0; o[1] = t1; o[2] = r0; o[3] = r1; o[4] = p0; o[5] = p1; o[6] = p2; o[7] = n;
     }
@@ -67,7 +67,7 @@ struct TailStamps {
   __device__ __forceinline__ void mark() { t[K] = stamp_clk(); }
   __device__ __forceinline__ ~TailStamps() {
     const unsigned long long re = stamp_real();
-    if (writer) {
+    if (writer && buf) {
 #pragma unroll
       for (int i = 0; i < 8; ++i) buf[(long long)wg * 16 + i] = t[i];
       buf[(long long)wg * 16 + 8] = re;

@@ -46,6 +46,8 @@ _SIGS = {
     "u3d_conv_small2": [I, P, I, I, I, I, I, P, I, P, P, P, I, P, P, P, L, P, P, P, P, P],
     "u3d_conv_small_gb_parts_floats": [I, I, I, I, I],
     "u3d_conv_small_dgrad_gn": [P, I, I, I, I, I, P, I, P, P, P, P, I, P, P, L, P, P, P, P, P, P, P],
+    "u3d_conv_small_bwd_pair_ok": [I, I, I, I, I, I, I, L],
+    "u3d_conv_small_bwd_pair": [P, I, I, I, I, I, P, I, P, P, P, P, I, P, P, L, P, P, P, P, P, I, P, I, P, P],
     "u3d_gn_bwd_apply_coef": [P, P, I, I, L, I, P, P, I, P],
     "u3d_conv_s2_ring_ok": [I, I, I, I, I, I],
     "u3d_conv32_ring_dgrad_gn_fused": [P, I, I, I, I, P, P, P, P, P, I, P, P, P, P, P, P, P],

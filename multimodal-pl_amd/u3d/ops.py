@@ -695,16 +695,23 @@ WGRAD_QUEUE = os.environ.get("U3D_WGRAD_QUEUE", "0") != "0"
 WGRAD_Q_WGS = 768
 
 
+def _wgrad_route(dy, x, k, stride):
+    """The weight-gradient kernel family conv_wgrad picks: "ring", True (halo bricks / the 1^3 kernel) or False."""
+    h, w_ = x.shape[2], x.shape[3]
+    brick = USE_BRICK_WGRAD and x.dtype == torch.bfloat16
+    if (brick and k == 3 and stride == 1 and USE_RING_WGRAD and min(h, w_) >= RING_WGRAD_MIN_HW
+            and max(x.numel() * x.element_size(), dy.numel() * dy.element_size()) < (1 << 31)):
+        brick = "ring"  # (the ring addresses its operands with 32-bit buffer offsets; larger ones: bricks)
+    return brick
+
+
 def conv_wgrad(dy, x, k, stride, gn=None, brick=None):
     """Returns (partials fp32 [nsplit, k^3, cout_p, cin_p], nsplit). bf16 3^3 convs use the halo-brick kernel."""
     n, d, h, w_, cin = x.shape
     cout = dy.shape[-1]
     st, ga, be, G = gn if gn is not None else (None, None, None, 0)
     if brick is None:
-        brick = USE_BRICK_WGRAD and x.dtype == torch.bfloat16
-        if (brick and k == 3 and stride == 1 and USE_RING_WGRAD and min(h, w_) >= RING_WGRAD_MIN_HW
-                and max(x.numel() * x.element_size(), dy.numel() * dy.element_size()) < (1 << 31)):
-            brick = "ring"  # (the ring addresses its operands with 32-bit buffer offsets; larger ones: bricks)
+        brick = _wgrad_route(dy, x, k, stride)
     if brick == "ring":
         assert k == 3 and stride == 1 and x.dtype == torch.bfloat16
         if WGRAD_QUEUE or collective_in_flight():  # short ranges the dispatcher deals to whichever CU is free
@@ -735,6 +742,59 @@ def conv_wgrad(dy, x, k, stride, gn=None, brick=None):
     call("u3d_conv_wgrad", dt_code(x.dtype), dy.data_ptr(), x.data_ptr(), n, cin, d, h, w_, cout, k, stride, _ptr(st),
          _ptr(ga), _ptr(be), G, part.data_ptr(), ns, _stream())
     return part, ns
+
+
+# Backward of a stride-1 3^3 conv behind GroupNorm + ReLU at the 12^3 / 6^3 levels: the data gradient (with its
+# GroupNorm-backward partials and finalize) and the weight gradient as two sub-grids of ONE launch
+# (u3d_conv_small_bwd_pair, small_pair.hip): weight-gradient workgroups take the CUs the data gradient's serial tail
+# leaves idle. Bitwise the two separate launches. U3D_SMALL_BWD_PAIR=0: the separate launches (A/B, tests).
+SMALL_BWD_PAIR = os.environ.get("U3D_SMALL_BWD_PAIR", "1") != "0"
+PAIR_CALLS = [0]  # launches of the pair (tests count them)
+
+
+def conv_bwd_pair_small(dy, pd, x, k, stride, gn, dgb):
+    """conv_wgrad(dy, x, k, stride, gn) and conv_dgrad_gn(dy, pd, cin, x, k, stride, gn, dgb) in one launch where the
+    first runs the 12 x 12-tile ring or the 3 x 8 x 16 brick and the second the small-volume kernel with the finalize
+    inside: returns (part, ns, dA, ("coef", coef)), or None (nothing launched, no output touched: the caller takes
+    the two calls). Off while a collective is in flight: the DDP-tolerant weight gradient splits differently."""
+    if not (SMALL_BWD_PAIR and gn is not None and not collective_in_flight() and not WGRAD_QUEUE):
+        return None
+    if x.dim() != 5 or dy.dim() != 5:
+        return None
+    n, d, h, w_, cin = x.shape
+    shape = (n, d, h, w_)
+    cout = dy.shape[-1]
+    if not (GN_BWD_FUSED and SMALL_GB and SMALL_FUSE and dy.dtype == torch.bfloat16 and x.dtype == torch.bfloat16
+            and k == 3 and stride == 1 and _use_small(dy.dtype, cout, cin, k, stride, shape) and cin % 8 == 0
+            and n * cin * 2 <= 8192):
+        return None  # (_conv_dgrad_gn_small's conditions)
+    if _use_conv32(dy.dtype, cin, cout, k, stride, n, w_):
+        return None  # (conv_dgrad_gn takes the 32-channel ring first)
+    route = _wgrad_route(dy, x, k, stride)
+    if not route:
+        return None
+    if os.environ.get("U3D_LIB") and not hasattr(_lib.lib(), "u3d_conv_small_bwd_pair"):
+        return None  # an A/B build of an older tree (_lib.lib)
+    ring = int(route == "ring")
+    ws = WS.get(SPLITK_WS_BYTES, dy.device, slot=4)
+    ns = query("u3d_conv_small_bwd_pair_ok", n, cout, d, h, w_, cin, ring, ws.numel())
+    if ns <= 0:
+        return None
+    st, ga, be, G = gn
+    dg, db = dgb()
+    da = torch.empty((n, d, h, w_, cin), dtype=dy.dtype, device=dy.device)
+    coef = torch.empty((n, 5, cin), dtype=torch.float32, device=dy.device)
+    part = torch.empty((ns, 27, round32(cout), round32(cin)), dtype=torch.float32, device=x.device)
+    cnt = WS.get(query("u3d_conv_small_cnt_bytes", n, d, h, w_, cin), dy.device, slot=SMALL_CNT_SLOT)
+    parts = WS.get(4 * query("u3d_conv_small_gb_parts_floats", n, d, h, w_, cin), dy.device, slot=SMALL_GB_SLOT)
+    made = ctypes.c_int(0)
+    call("u3d_conv_small_bwd_pair", dy.data_ptr(), n, cout, d, h, w_, pd.data_ptr(), cin, x.data_ptr(),
+         st.data_ptr(), ga.data_ptr(), be.data_ptr(), G, da.data_ptr(), ws.data_ptr(), ws.numel(), cnt.data_ptr(),
+         parts.data_ptr(), coef.data_ptr(), _ptr(dg), _ptr(db), ring, part.data_ptr(), ns, ctypes.addressof(made),
+         _stream())
+    assert made.value, "u3d_conv_small_bwd_pair declined a shape u3d_conv_small_bwd_pair_ok accepted"
+    PAIR_CALLS[0] += 1
+    return part, ns, da, ("coef", coef)
 
 
 # sum each weight gradient's slabs right after the launch that wrote them (round 5, cache-resident) instead of in the

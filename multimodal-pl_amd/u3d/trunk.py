@@ -198,7 +198,14 @@ class Tape:
                     if residual is not None:
                         self.acc_grad(residual, dy)
                     dyT = ops.cast(dy, self.dtype, pad_to=8)  # GEMM operand: channels padded to 8 (2-class head)
-                if xn is not None:
+                paired = None  # weight gradient + data gradient (GN backward inside) in one launch: 12^3 / 6^3 levels
+                if xn is None and gn is not None and not head and pair is None:
+                    paired = ops.conv_bwd_pair_small(dyT, pd, x.t, k, stride, gn,
+                                                     dgb=lambda: (self.grad_out(gn_key + ".weight", gn[1]),
+                                                                  self.grad_out(gn_key + ".bias", gn[2])))
+                if paired is not None:
+                    part, ns, dA, parts = paired
+                elif xn is not None:
                     part, ns = ops.conv_wgrad(dyT, xn, k, stride, None)
                 else:
                     part, ns = ops.conv_wgrad(dyT, x.t, k, stride, gn)
@@ -208,7 +215,8 @@ class Tape:
                 s2c = (gn is not None and pair == "park" and k == 1 and stride == 2 and ops.S2_COMPACT
                        and ops._use_conv1x1(dyT.dtype, dyT.shape[-1], cin, 1, dyT.shape[0])
                        and ops.s2_compact_ok(x.t.shape, cin, dyT.element_size()))
-                if gn is not None and not head and pair != "park" and not (pair == "finish" and x.gn_pend):
+                if paired is None and gn is not None and not head and pair != "park" \
+                        and not (pair == "finish" and x.gn_pend):
                     fused = ops.conv_dgrad_gn(dyT, pd, cin, x.t, k, stride, gn,  # GN-bwd partials in the epilogue
                                               dgb=lambda: (self.grad_out(gn_key + ".weight", gn[1]),
                                                            self.grad_out(gn_key + ".bias", gn[2])))

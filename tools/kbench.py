@@ -422,6 +422,30 @@ def _small_step(s, dg, c=256, n=2):
 for s_ in (12, 6):
     CASES[f"fwd{s_}st"] = (lambda s_=s_: _small_step(s_, False))
     CASES[f"dgrad{s_}gb"] = (lambda s_=s_: _small_step(s_, True))
+
+
+def _bwd_pair(s, c=256, n=2):
+    """the 12^3 / 6^3 backward of one conv: data gradient (+ GroupNorm backward) and weight gradient as one launch
+    (ops.conv_bwd_pair_small), next to the two separate launches on the same operands (printed on a line of its own)"""
+    x, pf, pd, g, r, dy, flop = conv_case(n, c, c, s, 3, 1, True, False)
+    dgam, dbet = torch.empty(c, device=dev), torch.empty(c, device=dev)
+    dgb = lambda: (dgam, dbet)  # noqa: E731
+
+    def separate():
+        ops.conv_wgrad(dy, x, 3, 1, g)
+        ops.conv_dgrad_gn(dy, pd, c, x, 3, 1, g, dgb=dgb)
+
+    def paired():
+        assert ops.conv_bwd_pair_small(dy, pd, x, 3, 1, g, dgb) is not None, "the pair declined"
+
+    us_sep = t_(separate)
+    us = t_(paired)
+    print(f"  separate launches (wgrad, then dgrad + GN backward) {us_sep:9.1f} us; one launch {us:9.1f} us", flush=True)
+    return us, 2 * flop
+
+
+CASES["bwdpair12"] = lambda: _bwd_pair(12)
+CASES["bwdpair6"] = lambda: _bwd_pair(6)
 CASES["headloss96"] = lambda: _head_loss(True)
 CASES["headloss96_2pass"] = lambda: _head_loss(False)
 CASES["headf96"] = lambda: _head(False)
