@@ -459,7 +459,9 @@ long long u3d_channel_sum_workspace_bytes(long long rows, int c);
  * logits fp32 [S][V][C] (NDHWC), labels fp32 [S][V] (integer-valued), weights fp32 [C] (= mask[0][:C]).
  * sums (fp64 [C][4]) = per class (sum p*t, sum p^2, sum t, sum BCE) over the whole batch; loss fp32[1].
  * uce: 0 = Dice only, 1 = + sum_c w_c BCE_c (EDiceLoss_partial), 2 = + cross entropy of the logits (softmax only;
- * nn.CrossEntropyLoss mean, unweighted: EDiceLoss_full, loss_partial.py:102-135). */
+ * nn.CrossEntropyLoss mean, unweighted: EDiceLoss_full, loss_partial.py:102-135). A label that equals no class
+ * index hits no class: its voxel counts as background for every class's BCE and has no cross-entropy term, in the
+ * forward and in the backward alike (the mean still divides by S * V). With uce 0, sums[c][3] is written as 0. */
 long long u3d_loss_workspace_bytes(int S, long long V, int C);
 int u3d_partial_loss_fwd(const float* logits, const float* labels, int S, long long V, int C, int softmax,
                          const float* weights, int uce, double* sums, float* loss, float* ws, u3d_stream_t stream);
@@ -581,7 +583,9 @@ int u3d_renew_token(int dtype, const void* x, long long sv, long long sc, int n,
 /* ---------------------------------------------------------------- consistency branch of get_loss (f2/f3)
  * losses.py:131-178: for every organ g with label_t[g] == 0 and every map k (natt attention maps through a sigmoid,
  * then softmax(logits)[g+1]) the soft Dice vs t = softmax(refine[g])[1] over the refiner-confident voxels
- * (t > 1-confi or t < confi), weighted [0.125,0.25,0.5,1][k] * weight_feature / (nt - supcount). Layouts by element
+ * (t > 1-confi or t < confi), weighted [0.125,0.25,0.5,1][k] * weight_feature / (nt - supcount). The reference
+ * enumerates the list maps + [softmax map], so with natt < 3 the softmax map is map number natt: it takes weight
+ * [..][natt] and passes through a sigmoid as well (only map number 3 skips it); dice / coef keep it in slot 3. Layouts by element
  * strides: att maps (organ att_sc, voxel att_sv), logits (voxel lsv, class lsc), refine (organ rsn, class rsc,
  * voxel rsv). Outputs: aux[1] (the weighted sum), dice [nt][4], coef [nt][4][2] (for the backward). Batch 1. */
 long long u3d_consistency_ws_bytes(int nt);

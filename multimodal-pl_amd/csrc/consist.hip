@@ -6,6 +6,8 @@
 // voxels where the refiner is confident (t > 1 - confi or t < confi):
 //   d_kg = 1 - (2 I + 1e-5) / (Z + Y + 1e-5),  I = sum s t, Z = sum s^2, Y = sum t^2
 //   aux  = sum_{k,g} d_kg * w_k * weight_feature / (num_classes - supcount),  w = [0.125, 0.25, 0.5, 1]
+// The reference enumerates attention maps + [softmax map] (:159-172): with natt < 3 attention maps the softmax map is
+// map number natt, so it takes w[natt] and, not being number 3, goes through a sigmoid like the others.
 // Forward: one pass per organ (grid.y) over the voxels -> fixed-order fp64 block partials -> a finalize kernel
 // forming aux and the per-(g,k) gradient coefficients A = 2/(Z+Y+eps), B = 2(2I+eps)/(Z+Y+eps)^2.
 // Backward: one elementwise pass: d map_k = c_k m (-A t + B s) s(1-s) (sigmoid maps), and the softmax map's
@@ -88,7 +90,8 @@ __global__ __launch_bounds__(256) void consist_fwd_kernel(ConsistArgs a, double*
       }
     }
     softmax_row(a, v, p);
-    const float s = p[g + 1];
+    float s = p[g + 1];
+    if (a.natt != 3) s = sigm(s);  // the reference's enumerate: only the map at index 3 skips the sigmoid
     acc[7] = fmaf(s, t, acc[7]);
     acc[8] = fmaf(s, s, acc[8]);
   }
@@ -128,7 +131,8 @@ __global__ void consist_finalize_kernel(const double* __restrict__ part, int nbl
       const float I = (float)s[1 + 2 * k], Z = (float)s[2 + 2 * k], Y = (float)s[0];
       const float den = Z + Y + 1e-5f;
       const float d = 1.f - (2.f * I + 1e-5f) / den;
-      const float c = present ? wk[k] * weight_feature / (float)(nt - sup) : 0.f;
+      // the softmax map (slot 3) is the reference's map number natt: weights[natt]
+      const float c = present ? wk[k == 3 ? natt : k] * weight_feature / (float)(nt - sup) : 0.f;
       dice[g * CS_MAPS + k] = present ? d : 0.f;
       coef[(g * CS_MAPS + k) * 2] = c * 2.f / den;
       coef[(g * CS_MAPS + k) * 2 + 1] = c * 2.f * (2.f * I + 1e-5f) / (den * den);
@@ -175,7 +179,12 @@ __global__ __launch_bounds__(256) void consist_bwd_kernel(ConsistArgs a, const f
       if (on && g + 1 < a.C) {
         const float s = p[g + 1];
         const float cA = coef[(g * CS_MAPS + 3) * 2], cB = coef[(g * CS_MAPS + 3) * 2 + 1];
-        gp[g + 1] = go * (cB * s - cA * t);
+        if (a.natt == 3) {
+          gp[g + 1] = go * (cB * s - cA * t);
+        } else {  // fewer than three attention maps: the softmax map went through a sigmoid too
+          const float q = sigm(s);
+          gp[g + 1] = go * (cB * q - cA * t) * q * (1.f - q);
+        }
       }
     }
     float dot = 0.f;

@@ -358,9 +358,14 @@ __global__ __launch_bounds__(LT) void loss_bwd_kernel(const float* __restrict__ 
     for (int c = 0; c < NC; ++c)
       r[c] = softmax == 1 ? p[c] * (g[c] - dot) : softmax == 0 ? g[c] * (1.f - p[c]) * p[c] : g[c];
     if (uce == 2) {  // cross entropy, in logit space: (softmax - onehot) / count
+      bool any = false;  // a label that matches no class has no term in the forward's sum, so none here
 #pragma unroll
-      for (int c = 0; c < NC; ++c)
-        if (c < C) r[c] += kb[c] * (p[c] - ((t == (float)c) ? 1.f : 0.f));
+      for (int c = 0; c < NC; ++c) any |= c < C && t == (float)c;
+      if (any) {
+#pragma unroll
+        for (int c = 0; c < NC; ++c)
+          if (c < C) r[c] += kb[c] * (p[c] - ((t == (float)c) ? 1.f : 0.f));
+      }
     }
     if constexpr (NC == 16 && sizeof(TO) == 4) {
 #pragma unroll

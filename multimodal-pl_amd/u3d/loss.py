@@ -245,7 +245,9 @@ def _lib_query(name, *a):
 
 
 def consistency_aux(logits, attns, refine, label_t, weight_feature, confi=0.10):
-    """aux term of get_loss's refiner branch (losses.py:158-174): one fused pass over the voxels per organ."""
+    """aux term of get_loss's refiner branch (losses.py:158-174): one fused pass over the voxels per organ.
+    As the reference enumerates ``attns + [softmax(output)[:, 1:]]``, with fewer than three attention maps the softmax
+    map is map number ``len(attns)``: it takes ``weights[len(attns)]`` and a sigmoid like the attention maps."""
     ops.require_device(logits, refine, *attns)
     if logits.shape[0] != 1:
         raise IndexError("get_loss consistency: the reference indexes the maps with a [1, 1, ...] mask "
