@@ -627,6 +627,56 @@ int u3d_aug_affine(float* x, long long V, float mul, float add, u3d_stream_t str
 int u3d_aug_contrast(float* x, long long V, float factor, const float* stats, int preserve_range,
                      u3d_stream_t stream);
 
+/* ---------------------------------------------------------------- style discriminators (csrc/disc.hip)
+ * get_style_discriminator_output (unet3D.py:1832-1849), deep_style_discriminator_output (:1852-1905),
+ * norm_style_discriminator_output (:1907-1947), as train_amos_atlas_final.py:320-379 drives them.
+ * Every activation is an NDHWC view (pointer, pitch in channels per voxel, first channel `off`); pitch and off are
+ * multiples of 8 and the base is 16-byte aligned, so a conv and its side conv write the two channel halves of one
+ * buffer (the torch.cat of :1896/:1900/:1903). d, h, w are always the layer's INPUT dims; the 4^3 / stride 2 / pad 1
+ * conv gives floor(n / 2) per dim and needs every dim >= 2. dy is the gradient of the layer's post-LeakyReLU output y;
+ * the kernels multiply it by lrelu'(y) (1 where y > 0, else 0.2) from the stored y. Fewer than 2^31 voxels per tensor.
+ *
+ * Inner conv (nn.Conv3d(cin, cout, 4, 2, 1) + LeakyReLU(0.2), :1818-1819 and its kin; cin, cout multiples of 32):
+ * wpk (dtype) [64][cin / 8][cout][8] (tap = (kd * 4 + kh) * 4 + kw); bias fp32 [cout]; splits = a power of two <= 64
+ * (u3d_disc_conv_fwd_splits), K split over whole taps, partial sums fp32 in ws and combined in split order. */
+int u3d_disc_conv_fwd_splits(int n, int d, int h, int w, int cin, int cout);
+long long u3d_disc_conv_fwd_ws_bytes(int n, int d, int h, int w, int cout, int splits);
+int u3d_disc_conv_fwd(int dtype, const void* x, int xp, int xo, int n, int d, int h, int w, int cin, const void* wpk,
+                      const float* bias, void* y, int yp, int yo, int cout, int splits, float* ws, u3d_stream_t stream);
+/* dx (dtype, view, cin channels, every voxel written) from dy, y (views, cout channels); wpk (dtype)
+ * [64][cout / 8][cin][8]. The 8 input-parity classes run in one launch. */
+int u3d_disc_conv_dgrad(int dtype, const void* dy, int dyp, int dyo, const void* y, int yp, int yo, int n, int d, int h,
+                        int w, int cin, int cout, const void* wpk, void* dx, int dxp, int dxo, u3d_stream_t stream);
+/* dw fp32 [cout][cin][4][4][4] (overwritten) from the layer input x and dy, y; ws: u3d_disc_conv_wgrad_ws_bytes bytes
+ * of fp32 slabs [splits][64][cout][cin], summed in split order (no atomics). */
+int u3d_disc_conv_wgrad_splits(int n, int d, int h, int w, int cin, int cout);
+long long u3d_disc_conv_wgrad_ws_bytes(int cin, int cout, int splits);
+int u3d_disc_conv_wgrad(int dtype, const void* x, int xp, int xo, const void* dy, int dyp, int dyo, const void* y, int yp,
+                        int yo, int n, int d, int h, int w, int cin, int cout, int splits, float* ws, float* dw,
+                        u3d_stream_t stream);
+/* db fp32 [C] = sum over the M voxels of dy * lrelu'(y), fixed-order block partials in ws */
+long long u3d_disc_bias_grad_ws_bytes(long long M, int C);
+int u3d_disc_bias_grad(int dtype, const void* dy, int dyp, int dyo, const void* y, int yp, int yo, long long M, int C,
+                       float* ws, float* db, u3d_stream_t stream);
+/* First layer (nn.Conv3d(num_classes, ndf, 4, 2, 1) + LeakyReLU, :1859-1860): x fp32 NCDHW [n][C][d][h][w], 1 <= C <= 4,
+ * w1 fp32 [64][C][cout]; dx fp32 NCDHW; dw fp32 [cout][C][4][4][4]. */
+int u3d_disc_first_fwd(int dtype, const float* x, int n, int C, int d, int h, int w, const float* w1, const float* bias,
+                       void* y, int yp, int yo, int cout, u3d_stream_t stream);
+int u3d_disc_first_dgrad(int dtype, const void* dy, int dyp, int dyo, const void* y, int yp, int yo, int n, int C, int d,
+                         int h, int w, int cout, const float* w1, float* dx, u3d_stream_t stream);
+long long u3d_disc_first_wgrad_ws_bytes(int n, int d, int h, int w, int C, int cout);
+int u3d_disc_first_wgrad(int dtype, const float* x, const void* dy, int dyp, int dyo, const void* y, int yp, int yo, int n,
+                         int C, int d, int h, int w, int cout, float* ws, float* dw, u3d_stream_t stream);
+/* Side conv (nn.Conv3d(1, C, 3, 1, 1) + LeakyReLU, :1861-1863): f fp32 [n][1][d][h][w], wsd fp32 [27][C]; df fp32 like
+ * f; dw fp32 [C][1][3][3][3]. */
+int u3d_disc_side_fwd(int dtype, const float* f, int n, int d, int h, int w, const float* wsd, const float* bias, void* y,
+                      int yp, int yo, int C, u3d_stream_t stream);
+int u3d_disc_side_dgrad(int dtype, const void* dy, int dyp, int dyo, const void* y, int yp, int yo, int n, int d, int h,
+                        int w, int C, const float* wsd, float* df, u3d_stream_t stream);
+long long u3d_disc_side_wgrad_ws_bytes(int n, int d, int h, int w, int C);
+int u3d_disc_side_wgrad(int dtype, const float* f, const void* dy, int dyp, int dyo, const void* y, int yp, int yo, int n,
+                        int d, int h, int w, int C, float* ws, float* dw, u3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

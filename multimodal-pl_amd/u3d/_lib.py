@@ -139,11 +139,29 @@ _SIGS = {
     "u3d_aug_blur_axis": [P, P, L, I, L, P, I, P],
     "u3d_aug_affine": [P, L, F, F, P],
     "u3d_aug_contrast": [P, L, F, P, I, P],
+    "u3d_disc_conv_fwd_splits": [I, I, I, I, I, I],
+    "u3d_disc_conv_fwd_ws_bytes": [I, I, I, I, I, I],
+    "u3d_disc_conv_fwd": [I, P, I, I, I, I, I, I, I, P, P, P, I, I, I, I, P, P],
+    "u3d_disc_conv_dgrad": [I, P, I, I, P, I, I, I, I, I, I, I, I, P, P, I, I, P],
+    "u3d_disc_conv_wgrad_splits": [I, I, I, I, I, I],
+    "u3d_disc_conv_wgrad_ws_bytes": [I, I, I],
+    "u3d_disc_conv_wgrad": [I, P, I, I, P, I, I, P, I, I, I, I, I, I, I, I, I, P, P, P],
+    "u3d_disc_bias_grad_ws_bytes": [L, I],
+    "u3d_disc_bias_grad": [I, P, I, I, P, I, I, L, I, P, P, P],
+    "u3d_disc_first_fwd": [I, P, I, I, I, I, I, P, P, P, I, I, I, P],
+    "u3d_disc_first_dgrad": [I, P, I, I, P, I, I, I, I, I, I, I, I, P, P, P],
+    "u3d_disc_first_wgrad_ws_bytes": [I, I, I, I, I, I],
+    "u3d_disc_first_wgrad": [I, P, P, I, I, P, I, I, I, I, I, I, I, I, P, P, P],
+    "u3d_disc_side_fwd": [I, P, I, I, I, I, P, P, P, I, I, I, P],
+    "u3d_disc_side_dgrad": [I, P, I, I, P, I, I, I, I, I, I, I, P, P, P],
+    "u3d_disc_side_wgrad_ws_bytes": [I, I, I, I, I],
+    "u3d_disc_side_wgrad": [I, P, P, I, I, P, I, I, I, I, I, I, I, P, P, P],
 }
 _RESTYPE = {"u3d_stem_fwd_ws_bytes": L, "u3d_stem1_stats_ws_floats": L, "u3d_conv_small_cnt_bytes": L, "u3d_conv_small_spart_floats": L, "u3d_conv_small_gb_parts_floats": L, "u3d_conv_s2_ring_ws_floats": L, "u3d_upsample2x_stats_ws_floats": L, "u3d_wstd_bwd_scratch_bytes": L, "u3d_gn_workspace_bytes": L, "u3d_channel_sum_workspace_bytes": L, "u3d_loss_workspace_bytes": L,
             "u3d_eam_attn_bwd_part_floats": L, "u3d_upsample_trilinear_bwd_ws_floats": L, "u3d_renew_token_ws_bytes": L,
             "u3d_consistency_ws_bytes": L, "u3d_volume_stats_ws_bytes": L, "u3d_convg_brick_stats_ws_floats": L,
-            "u3d_deepsup_loss_workspace_bytes": L}
+            "u3d_deepsup_loss_workspace_bytes": L, "u3d_disc_conv_fwd_ws_bytes": L, "u3d_disc_conv_wgrad_ws_bytes": L,
+            "u3d_disc_bias_grad_ws_bytes": L, "u3d_disc_first_wgrad_ws_bytes": L, "u3d_disc_side_wgrad_ws_bytes": L}
 
 _lib = None
 

@@ -375,11 +375,107 @@ class unet3D_with_deepsup(_TrunkMixin, nn.Module):
         return outs
 
 
-# Method-specific variants and discriminators: next rows, not on the trunk path.
+# Method-specific variants: next rows, not on the trunk path. get_style_discriminator (a
+# (2, 3, 2) conv) is not built by the driver.
 unet3D_with_feam = _next_row("unet3D_with_feam", "f2")
 unet3D_with_eam = _next_row("unet3D_with_eam", "f2")
 unet3D_with_eam_baseline = _next_row("unet3D_with_eam_baseline", "f2")
 get_style_discriminator = _next_row("get_style_discriminator", "out-of-scope")
-get_style_discriminator_output = _next_row("get_style_discriminator_output", "out-of-scope")
-deep_style_discriminator_output = _next_row("deep_style_discriminator_output", "out-of-scope")
-norm_style_discriminator_output = _next_row("norm_style_discriminator_output", "out-of-scope")
+
+
+class Reshape(nn.Module):
+    """Reference unet3D.py:1825-1830."""
+
+    def forward(self, x):
+        return x.view(x.shape[0], -1)
+
+
+def _lrelu():
+    return nn.LeakyReLU(negative_slope=0.2, inplace=True)
+
+
+def _disc_conv(cin, cout):
+    return nn.Conv3d(cin, cout, kernel_size=4, stride=2, padding=1)
+
+
+def _disc_tail(cin, ndf, out_features):
+    """block4 of the two discriminator classes / the back of get_style_discriminator_output: three 4^3 stride-2 convs,
+    pool, reshape, linear (reference unet3D.py:1879-1889), at the reference's Sequential indices."""
+    return [_disc_conv(cin, ndf * 8), _lrelu(), _disc_conv(ndf * 8, ndf * 8), _lrelu(), _disc_conv(ndf * 8, ndf * 8),
+            _lrelu(), nn.AdaptiveAvgPool3d(1), Reshape(), nn.Linear(ndf * 8, out_features)]
+
+
+def _wb(conv):
+    return conv.weight, conv.bias
+
+
+class _StyleDiscriminatorOutput(nn.Sequential):
+    """What get_style_discriminator_output returns (reference unet3D.py:1832-1849): the reference's nn.Sequential, same
+    indices and state_dict keys, with the forward on the native kernels (u3d.disc)."""
+
+    def __init__(self, num_classes, ndf):
+        from u3d import disc
+        disc.check_config(num_classes, ndf)
+        super().__init__(_disc_conv(num_classes, ndf), _lrelu(), _disc_conv(ndf, ndf * 2), _lrelu(),
+                         _disc_conv(ndf * 2, ndf * 4), _lrelu(), *_disc_tail(ndf * 4, ndf, 1))
+        self.num_classes, self.ndf = num_classes, ndf
+
+    def forward(self, x_in):
+        from u3d import disc
+        feat = disc.run_chain(x_in, None, [_wb(self[i]) for i in (0, 2, 4, 6, 8, 10)], None, self.num_classes, self.ndf)
+        return disc.pool_linear(feat, self[14].weight, self[14].bias)
+
+
+def get_style_discriminator_output(num_classes, ndf=32):
+    """Reference unet3D.py:1832-1849. forward(x_in [B, num_classes, D, H, W]) -> [B, 1]."""
+    return _StyleDiscriminatorOutput(num_classes, ndf)
+
+
+class deep_style_discriminator_output(nn.Module):
+    """Reference unet3D.py:1852-1905 (train_amos_atlas_final.py:124): forward(x_in, f_m) -> [B, 2]; f_m[2] / f_m[1] /
+    f_m[0] are one-channel maps at block1's / block2's / block3's output resolution. The side convs write the upper
+    channel half of the buffer the next block reads: the reference's torch.cat is never materialised."""
+
+    def __init__(self, num_classes, ndf=32):
+        from u3d import disc
+        disc.check_config(num_classes, ndf)
+        super().__init__()
+        self.ndf = ndf
+        self._num_classes = num_classes
+        self.block1 = nn.Sequential(_disc_conv(num_classes, ndf), _lrelu())
+        self.min_block1 = nn.Sequential(nn.Conv3d(1, ndf, kernel_size=3, stride=1, padding=1), _lrelu())
+        self.block2 = nn.Sequential(_disc_conv(ndf * 2, ndf * 2), _lrelu())
+        self.min_block2 = nn.Sequential(nn.Conv3d(1, ndf * 2, kernel_size=3, stride=1, padding=1), _lrelu())
+        self.block3 = nn.Sequential(_disc_conv(ndf * 4, ndf * 4), _lrelu())
+        self.min_block3 = nn.Sequential(nn.Conv3d(1, ndf * 4, kernel_size=3, stride=1, padding=1), _lrelu())
+        self.block4 = nn.Sequential(*_disc_tail(ndf * 8, ndf, 2))
+
+    def forward(self, x_in, f_m):
+        from u3d import disc
+        b4 = self.block4
+        convs = [_wb(self.block1[0]), _wb(self.block2[0]), _wb(self.block3[0]), _wb(b4[0]), _wb(b4[2]), _wb(b4[4])]
+        sides = [_wb(self.min_block1[0]), _wb(self.min_block2[0]), _wb(self.min_block3[0])]
+        feat = disc.run_chain(x_in, f_m, convs, sides, self._num_classes, self.ndf)
+        return disc.pool_linear(feat, b4[8].weight, b4[8].bias)
+
+
+class norm_style_discriminator_output(nn.Module):
+    """Reference unet3D.py:1907-1947 (train_amos_atlas_final.py:126): forward(x_in) -> [B, 2]."""
+
+    def __init__(self, num_classes, ndf=32):
+        from u3d import disc
+        disc.check_config(num_classes, ndf)
+        super().__init__()
+        self.ndf = ndf
+        self._num_classes = num_classes
+        self.block1 = nn.Sequential(_disc_conv(num_classes, ndf), _lrelu())
+        self.block2 = nn.Sequential(_disc_conv(ndf, ndf * 2), _lrelu())
+        self.block3 = nn.Sequential(_disc_conv(ndf * 2, ndf * 4), _lrelu())
+        self.block4 = nn.Sequential(*_disc_tail(ndf * 4, ndf, 2))
+
+    def forward(self, x_in):
+        from u3d import disc
+        b4 = self.block4
+        convs = [_wb(self.block1[0]), _wb(self.block2[0]), _wb(self.block3[0]), _wb(b4[0]), _wb(b4[2]), _wb(b4[4])]
+        feat = disc.run_chain(x_in, None, convs, None, self._num_classes, self.ndf)
+        return disc.pool_linear(feat, b4[8].weight, b4[8].bias)
