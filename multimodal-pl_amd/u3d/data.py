@@ -27,7 +27,7 @@ def volume_stats(x, count=None):
     order)."""
     x = x.float().contiguous()
     out = torch.empty(4, dtype=torch.float32, device=x.device)
-    ws = ops.WS.get(query("u3d_volume_stats_ws_bytes"), x.device, slot=11)
+    ws = ops.WS.get(query("u3d_volume_stats_ws_bytes"), x.device, ops.Slot.VOLUME_STATS)
     call("u3d_volume_stats", x.data_ptr(), x.numel(), int(count or x.numel()), out.data_ptr(), ws.data_ptr(),
          ops._stream())
     return out

@@ -90,7 +90,7 @@ class View:
 
 
 def _ws(nbytes, device):
-    return WS.get(max(int(nbytes), 256), device, slot="disc")
+    return WS.get(max(int(nbytes), 256), device, ops.Slot.DISC)
 
 
 def conv_fwd(x, wpk, bias, y):

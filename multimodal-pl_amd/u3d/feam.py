@@ -222,6 +222,7 @@ def renew_token(tokens, features, mask, num_classes, alpha):
         if feat.dtype not in (torch.float32, torch.bfloat16):
             feat = feat.float()
         ops.require_device(feat)
-        ws = ops.WS.get(query("u3d_renew_token_ws_bytes", n, d, h, w, num_classes, c), feat.device, slot=6)
+        ws = ops.WS.get(query("u3d_renew_token_ws_bytes", n, d, h, w, num_classes, c), feat.device,
+                        ops.Slot.RENEW_TOKEN)
         call("u3d_renew_token", ops.dt_code(feat.dtype), feat.data_ptr(), sv, sc, n, d, h, w, c, mask.data_ptr(),
              md, mh, mw, num_classes, tok.shape[0], float(alpha), tok.data_ptr(), ws.data_ptr(), ops._stream())

@@ -100,7 +100,6 @@ def partial_loss(logits, target, weights, mode=MODE_SOFTMAX, uce=True):
 
 # ------------------------------------------------------------------ deep supervision (losses.py:119-129)
 DEEP_WEIGHTS = (0.125, 0.25, 0.5, 1.0)   # losses.py:116
-DEEPSUP_SLOT = 10
 
 
 def _deepsup_host_args(lgs, level_weights):
@@ -123,7 +122,7 @@ class _DeepSupFn(torch.autograd.Function):
         sums = torch.empty((L, C, 4), dtype=torch.float64, device=dev)
         level_loss = torch.empty(L, dtype=torch.float32, device=dev)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
-        ws = ops.WS.get(_lib_query("u3d_deepsup_loss_workspace_bytes", L, C), dev, slot=DEEPSUP_SLOT)
+        ws = ops.WS.get(_lib_query("u3d_deepsup_loss_workspace_bytes", L, C), dev, ops.Slot.DEEPSUP)
         ptrs, dims, lw = _deepsup_host_args(lgs, level_weights)
         ops.call("u3d_deepsup_loss_fwd", L, ptrs, dims, lw, tgt.data_ptr(), S, D, H, W, C, weights.data_ptr(),
                  sums.data_ptr(), level_loss.data_ptr(), loss.data_ptr(), ws.data_ptr(), ops._stream())
@@ -213,7 +212,7 @@ class _ConsistFn(torch.autograd.Function):
         aux = torch.empty(1, dtype=torch.float32, device=dev)
         dice = torch.empty((nt, 4), dtype=torch.float32, device=dev)
         coef = torch.empty((nt, 4, 2), dtype=torch.float32, device=dev)
-        ws = ops.WS.get(_lib_query("u3d_consistency_ws_bytes", nt), dev, slot=7)
+        ws = ops.WS.get(_lib_query("u3d_consistency_ws_bytes", nt), dev, ops.Slot.CONSISTENCY)
         ops.call("u3d_consistency_fwd", ptr[0], ptr[1], ptr[2], len(aa), asc, asv, lg.data_ptr(), lsv, lsc, C,
                  ref.data_ptr(), rsn, rsc, rsv, lt.data_ptr(), nt, V, float(confi), float(weight_feature),
                  aux.data_ptr(), dice.data_ptr(), coef.data_ptr(), ws.data_ptr(), ops._stream())
@@ -270,7 +269,7 @@ class _Full2Fn(torch.autograd.Function):
         V = xc.numel()
         loss = torch.empty(1, dtype=torch.float32, device=x.device)
         coef = torch.empty(3, dtype=torch.float32, device=x.device)
-        ws = ops.WS.get(128 * 4 * 8, x.device, slot=8)
+        ws = ops.WS.get(128 * 4 * 8, x.device, ops.Slot.EDICE)
         ops.call("u3d_edice_full2_fwd", xc.data_ptr(), tc.data_ptr(), mc.data_ptr() if mc is not None else None, V,
                  int(sigmoid), int(uce), loss.data_ptr(), coef.data_ptr(), ws.data_ptr(), ops._stream())
         ctx.save_for_backward(xc, tc, coef, *( [mc] if mc is not None else []))

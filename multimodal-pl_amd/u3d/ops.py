@@ -2,13 +2,13 @@
 value is computed by a HIP kernel. All activations are NDHWC tensors of shape [n, d, h, w, c]."""
 import contextlib
 import ctypes
+import enum
 import os
 
 import torch
 
 from . import _lib
 from ._lib import BF16, F32, call, query
-
 
 
 def get_option(name):
@@ -42,6 +42,16 @@ def option(name, value):
 
 def _ptr(t):
     return None if t is None else t.data_ptr()
+
+
+def _gn4(gn):
+    """(stats, gamma, beta, groups) of a GroupNorm + ReLU prologue; without one: null pointers and 0 groups."""
+    return gn if gn is not None else (None, None, None, 0)
+
+
+def _dst(dx, accumulate, like):
+    """(destination, accumulate): a fresh destination shaped like ``like`` has nothing to accumulate onto."""
+    return (torch.empty_like(like), False) if dx is None else (dx, accumulate)
 
 
 _RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -80,16 +90,51 @@ def out_dim(d, k, s):
     return (d + 2 * (k // 2) - k) // s + 1
 
 
+@enum.unique
+class Slot(enum.Enum):
+    """Every slot of WS: one grow-only buffer each, its users stream-ordered. Shared on purpose: SPLITK (the split-K
+    slabs of the implicit GEMM, the small-volume kernels and the backward pair) and CONV_STATS (the epilogue statistics
+    partials of the ring and of the persistent brick). ZERO: holds completion counters / claim words, zero when
+    allocated and left zero by every launch; nothing else may write there (it would corrupt results silently)."""
+    GN = 1               # GroupNorm kernels. ZERO (the first 256 B)
+    CHANNEL_SUM = 2
+    LOSS = 3
+    SPLITK = 4
+    WSTD_BWD = 5
+    RENEW_TOKEN = 6      # feam
+    CONSISTENCY = 7      # loss
+    EDICE = 8            # loss
+    CONV_STATS = 9
+    DEEPSUP = 10         # loss
+    VOLUME_STATS = 11    # data
+    STEM = 13            # the conv1 kernel's fp32 weight table
+    STEM_STATS = 14
+    UP_STATS = 15
+    SMALL_CNT = 16       # ZERO: conv_small's per-tile arrival counters
+    SMALL_SPART = 17
+    RING_CNT = 18        # ZERO
+    BRICK_CNT = 19       # ZERO
+    SMALL_GB = 20        # GroupNorm-backward partials of the small-volume data gradient
+    S2_SPART = 21
+    S2_CNT = 22          # ZERO
+    RING_GB_CNT = 23     # ZERO
+    HEAD_CNT = 24        # ZERO: the GN head backward's arrival counter
+    QUEUE = 40           # ZERO: claim words of the work-stealing ring
+    DISC = "disc"        # the discriminator kernels' scratch
+
+
+SMALL_GB_SLOT, QUEUE_SLOT = Slot.SMALL_GB.value, Slot.QUEUE.value  # (read by tests)
+
+
 class _WS:
-    """Grow-only per-device scratch buffer (device memory owned by torch's caching allocator). Zero-filled when
-    (re)allocated: the GroupNorm kernels keep completion counters at the head of their workspace and leave
-    them at zero after every launch."""
+    """Grow-only per-device scratch buffers (device memory owned by torch's caching allocator), one per Slot.
+    Zero-filled when (re)allocated: the ZERO slots rely on it."""
 
     def __init__(self):
         self.buf = {}
 
-    def get(self, nbytes, device, slot=0):
-        key = (device, slot)
+    def get(self, nbytes, device, slot):
+        key = (device, Slot(slot).value)  # (a member or its number; a number not in the table raises)
         b = self.buf.get(key)
         if b is None or b.numel() < nbytes:
             b = torch.zeros(max(int(nbytes), 256), dtype=torch.uint8, device=device)
@@ -191,21 +236,21 @@ def wstd_bwd_batch(items):
     for i in range(0, len(descs), _lib.WSTD_BATCH_MAX):
         chunk = descs[i:i + _lib.WSTD_BATCH_MAX]
         arr = (_lib.WstdDesc * len(chunk))(*chunk)
-        ws = WS.get(query("u3d_wstd_bwd_scratch_bytes", ctypes.addressof(arr), len(chunk)), dev, slot=5)
+        ws = WS.get(query("u3d_wstd_bwd_scratch_bytes", ctypes.addressof(arr), len(chunk)), dev, Slot.WSTD_BWD)
         call("u3d_wstd_bwd_batch", ctypes.addressof(arr), len(chunk), ws.data_ptr(), _stream())
 
 
 def wstd_bwd(partials, nsplit, w, wstats, standardize, dw=None, accumulate=False):
     cout, cin, k = w.shape[0], w.shape[1], w.shape[2]
-    if dw is None:
-        dw = torch.empty_like(w)
-        accumulate = False
+    dw, accumulate = _dst(dw, accumulate, w)
     call("u3d_wstd_bwd", partials.data_ptr(), nsplit, w.data_ptr(), _ptr(wstats), cout, cin, k, int(standardize),
          dw.data_ptr(), int(accumulate), _stream())
     return dw
 
 
 # ------------------------------------------------------------------------------------------ convs
+# The kernel families and their applicability tests. conv_route (below) is the only place that orders them; every
+# fused form names the family it extends and its extra conditions.
 # bf16 1^3 convs (stride 1 / 2, GN prologue in registers) and stride-1 1^3 data gradients: streaming kernel
 # (conv1x1.hip) instead of the implicit GEMM (+ GN materialisation). U3D_CONV1X1=0: the implicit GEMM.
 USE_CONV1X1 = os.environ.get("U3D_CONV1X1", "1") != "0"
@@ -216,253 +261,6 @@ def _use_conv1x1(dtype, cx, cy, k, n):
         and n <= 65535
 
 
-def conv_fwd(x, wpk, cout, k, stride, gn=None, residual=None, bias=None, out_f32=False):
-    """x: [n,d,h,w,cin] -> [n,od,oh,ow,cout]. gn = (stats, gamma, beta, groups) fuses GroupNorm+ReLU."""
-    require_device(x)
-    n, d, h, w_, cin = x.shape
-    od, oh, ow = out_dim(d, k, stride), out_dim(h, k, stride), out_dim(w_, k, stride)
-    y = torch.empty((n, od, oh, ow, cout), dtype=torch.float32 if out_f32 else x.dtype, device=x.device)
-    st, ga, be, G = gn if gn is not None else (None, None, None, 0)
-    if _use_conv1x1(x.dtype, cin, cout, k, n) and residual is None and bias is None and not out_f32:
-        call("u3d_conv1x1", x.data_ptr(), n, cin, d, h, w_, wpk.data_ptr(), wpk.shape[-1], cout, stride, _ptr(st),
-             _ptr(ga), _ptr(be), G, y.data_ptr(), _stream())
-        return y
-    if _use_conv32(x.dtype, cin, cout, k, stride, n, w_) and _conv32_fits(x) and not out_f32 and bias is None:
-        pr = _probe0()
-        if _ring_queue():
-            call("u3d_conv32_ring_q", 0, x.data_ptr(), n, d, h, w_, wpk.data_ptr(), _ptr(st), _ptr(ga), _ptr(be), G,
-                 _ptr(residual), y.data_ptr(), None, _queue(x.device, (n, d, h, w_)), _stream())
-        else:
-            call(CONV32_FN, 0, x.data_ptr(), n, d, h, w_, wpk.data_ptr(), _ptr(st), _ptr(ga), _ptr(be), G,
-                 _ptr(residual), y.data_ptr(), _stream())
-        _probe1(pr, "conv32_ring fwd" + (" GN" if st is not None else "") + (" +res" if residual is not None else ""),
-                2.0 * n * d * h * w_ * 27 * 32 * 32, n * d * h * w_)
-        return y
-    if _use_small(x.dtype, cin, cout, k, stride, (n, d, h, w_)) and not out_f32 and bias is None:
-        conv_small(0, x, cin, wpk, cout, (st, ga, be, G), residual, y)
-        return y
-    if _use_gen_brick(x.dtype, cin, cout, k, stride, (n, d, h, w_)) and not out_f32 and bias is None:
-        call("u3d_convg_brick", 0, x.data_ptr(), n, cin, d, h, w_, wpk.data_ptr(), cout, _ptr(st), _ptr(ga), _ptr(be),
-             G, _ptr(residual), y.data_ptr(), _stream())
-        return y
-    if (st is not None and x.dtype == torch.bfloat16 and cin >= GN_MATERIALIZE_MIN_C
-            and x.numel() * 2 <= GN_MATERIALIZE_BYTES):
-        # small deep-layer activation: materialise relu(gn(x)) once so the GEMM K loop has no GN arithmetic
-        x = gn_apply(x, st, ga, be, G)
-        st = ga = be = None
-        G = 0
-    ws = WS.get(SPLITK_WS_BYTES, x.device, slot=4)
-    call("u3d_conv_fwd", dt_code(x.dtype), x.data_ptr(), n, cin, d, h, w_, wpk.data_ptr(), cout, k, stride, _ptr(st),
-         _ptr(ga), _ptr(be), G, _ptr(residual), _ptr(bias), y.data_ptr(), int(out_f32), ws.data_ptr(), ws.numel(),
-         _stream())
-    return y
-
-
-# conv_small's split-K slabs combined inside its launch by each output tile's last-arriving workgroup (round 5,
-# u3d_conv_small2: no small_reduce_kernel launch); U3D_SMALL_FUSE=0: the two-kernel form
-SMALL_FUSE = os.environ.get("U3D_SMALL_FUSE", "1") != "0"
-SMALL_CNT_SLOT, SMALL_SPART_SLOT = 16, 17
-
-
-def conv_small(flip, x, cin, wpk, cout, gn, residual, y, want_stats=False):
-    """u3d_conv_small(2) into y; returns the output's GroupNorm(16) statistics [n,16,2] when want_stats and the launch
-    produced them (in-kernel combine with the contraction split), else None."""
-    n, d, h, w_ = x.shape[:4]
-    st, ga, be, G = gn if gn is not None else (None, None, None, 0)
-    ws = WS.get(SPLITK_WS_BYTES, x.device, slot=4)
-    if not SMALL_FUSE:
-        call("u3d_conv_small", flip, x.data_ptr(), n, cin, d, h, w_, wpk.data_ptr(), cout, _ptr(st), _ptr(ga),
-             _ptr(be), G, _ptr(residual), y.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
-        return None
-    cnt = WS.get(query("u3d_conv_small_cnt_bytes", n, d, h, w_, cout), x.device, slot=SMALL_CNT_SLOT)
-    stats = sp = None
-    if want_stats:
-        stats = torch.empty((n, 16, 2), dtype=torch.float32, device=x.device)
-        sp = WS.get(4 * query("u3d_conv_small_spart_floats", n, d, h, w_), x.device, slot=SMALL_SPART_SLOT)
-    made = ctypes.c_int(0)
-    call("u3d_conv_small2", flip, x.data_ptr(), n, cin, d, h, w_, wpk.data_ptr(), cout, _ptr(st), _ptr(ga), _ptr(be),
-         G, _ptr(residual), y.data_ptr(), ws.data_ptr(), ws.numel(), cnt.data_ptr(), _ptr(sp), _ptr(stats),
-         ctypes.addressof(made), _stream())
-    return stats if made.value else None
-
-
-# the forward ring stores relu(gn(x)) for the weight gradient (round 6; measured slower, off: the forward rings pay
-# +16-19 us per launch for the side stores, the GN-free weight gradient saves 7.5 us per launch; step 5.76 vs 5.62 ms)
-RING_XN = os.environ.get("U3D_RING_XN", "0") != "0"
-
-
-def ring_xn_ok(x, cout, k, stride, gn):
-    """Whether conv_fwd_stats_xn applies: the static 32->32 ring forward with its GroupNorm prologue (bf16)."""
-    n, d, h, w_, cin = x.shape
-    return (RING_XN and RING_STATS and gn is not None and cout == 32 and CONV32_FN == "u3d_conv32_ring"
-            and not FUSED_FINALIZE and not _ring_queue() and _use_conv32(x.dtype, cin, cout, k, stride, n, w_)
-            and _conv32_fits(x))
-
-
-# stride-2 3^3 convs with cin >= 64 (the 48^3 / 24^3 / 12^3 downsampling convs on the implicit GEMM): normalise the
-# input once (round 6, kbench gpurun_out/r06_g: 48^3 forward 65.5 -> 48.4 + 14.1 us, its weight gradient 36.0 -> 30.2)
-S2_NORM_ONCE = os.environ.get("U3D_S2_NORM_ONCE", "1") != "0"
-
-
-def s2_normalise_once(x, cin, cout, k, stride, gn):
-    return (S2_NORM_ONCE and gn is not None and k == 3 and stride == 2 and x.dtype == torch.bfloat16 and cin >= 64
-            and cin % 8 == 0 and not (S2_RING and cin == 32 and cout == 64))
-
-
-def conv_fwd_stats_xn(x, wpk, cout, k, stride, gn, residual=None):
-    """conv_fwd_stats on the static ring that also returns xn = relu(gn(x)) (bf16 NDHWC, x's shape), stored by the
-    ring from its staged input: the conv's weight gradient then reads xn without a GroupNorm prologue (bitwise the
-    same partials as conv_wgrad(dy, x, ..., gn)). Caller checks ring_xn_ok. Returns (y, stats, xn)."""
-    n, d, h, w_, cin = x.shape
-    st, ga, be, G = gn
-    y = torch.empty((n, d, h, w_, cout), dtype=x.dtype, device=x.device)
-    xn = torch.empty_like(x)
-    stats = torch.empty((n, 16, 2), dtype=torch.float32, device=x.device)
-    ws = WS.get(4 * query("u3d_conv32_ring_stats_ws_floats", n), x.device, slot=9)
-    pr = _probe0()
-    call("u3d_conv32_ring_stats_xn", x.data_ptr(), n, d, h, w_, wpk.data_ptr(), st.data_ptr(), ga.data_ptr(),
-         be.data_ptr(), G, _ptr(residual), y.data_ptr(), xn.data_ptr(), ws.data_ptr(), _stream())
-    _probe1(pr, "conv32_ring fwd GN" + (" +res" if residual is not None else "") + " +stats",
-            2.0 * n * d * h * w_ * 27 * 32 * 32, n * d * h * w_)
-    call("u3d_conv32_ring_stats_finalize", ws.data_ptr(), n, d, h, w_, stats.data_ptr(), _stream())
-    return y, stats, xn
-
-
-def conv_fwd_stats(x, wpk, cout, k, stride, gn=None, residual=None):
-    """conv_fwd that also returns the GroupNorm(16) statistics [n,16,2] of its output when the 32->32 ring kernel
-    runs with a GN prologue (epilogue-accumulated); otherwise (conv_fwd(...), None)."""
-    n, d, h, w_, cin = x.shape
-    if (RING_STATS and gn is not None and cout == 32 and CONV32_FN == "u3d_conv32_ring"
-            and _use_conv32(x.dtype, cin, cout, k, stride, n, w_) and _conv32_fits(x)):
-        st, ga, be, G = gn
-        y = torch.empty((n, d, h, w_, cout), dtype=x.dtype, device=x.device)
-        stats = torch.empty((n, 16, 2), dtype=torch.float32, device=x.device)
-        q = _ring_queue()
-        nws = query("u3d_conv32_ring_q_stats_ws_floats", n, d, h, w_) if q else query("u3d_conv32_ring_stats_ws_floats", n)
-        ws = WS.get(4 * nws, x.device, slot=9)
-        pr = _probe0()
-        if q:
-            call("u3d_conv32_ring_q", 0, x.data_ptr(), n, d, h, w_, wpk.data_ptr(), st.data_ptr(), ga.data_ptr(),
-                 be.data_ptr(), G, _ptr(residual), y.data_ptr(), ws.data_ptr(), _queue(x.device, (n, d, h, w_)), _stream())
-        elif FUSED_FINALIZE:  # the statistics finalized by the launch's last-arriving workgroup (round 5)
-            call("u3d_conv32_ring_stats_fused", x.data_ptr(), n, d, h, w_, wpk.data_ptr(), st.data_ptr(), ga.data_ptr(),
-                 be.data_ptr(), G, _ptr(residual), y.data_ptr(), ws.data_ptr(), stats.data_ptr(),
-                 WS.get(256, x.device, slot=RING_CNT_SLOT).data_ptr(), _stream())
-        else:
-            call("u3d_conv32_ring_stats", x.data_ptr(), n, d, h, w_, wpk.data_ptr(), st.data_ptr(), ga.data_ptr(),
-                 be.data_ptr(), G, _ptr(residual), y.data_ptr(), ws.data_ptr(), _stream())
-        _probe1(pr, "conv32_ring fwd GN" + (" +res" if residual is not None else "") + " +stats",
-                2.0 * n * d * h * w_ * 27 * 32 * 32, n * d * h * w_)
-        if q or not FUSED_FINALIZE:
-            fin = "u3d_conv32_ring_q_stats_finalize" if q else "u3d_conv32_ring_stats_finalize"
-            call(fin, ws.data_ptr(), n, d, h, w_, stats.data_ptr(), _stream())
-        return y, stats
-    if (S2_RING and gn is not None and residual is None and k == 3 and stride == 2 and x.dtype == torch.bfloat16
-            and cin == 32 and cout == 64 and query("u3d_conv_s2_ring_ok", n, cin, d, h, w_, cout)):
-        # stride-2 forward as an input-plane walk, GN applied once per staged element, output statistics in-kernel
-        st, ga, be, G = gn
-        od, oh, ow = out_dim(d, 3, 2), out_dim(h, 3, 2), out_dim(w_, 3, 2)
-        y = torch.empty((n, od, oh, ow, cout), dtype=x.dtype, device=x.device)
-        stats = torch.empty((n, 16, 2), dtype=torch.float32, device=x.device)
-        sp = WS.get(4 * query("u3d_conv_s2_ring_ws_floats", n, d, h, w_), x.device, slot=S2_SPART_SLOT)
-        call("u3d_conv_s2_ring", x.data_ptr(), n, d, h, w_, wpk.data_ptr(), st.data_ptr(), ga.data_ptr(), be.data_ptr(),
-             G, y.data_ptr(), sp.data_ptr(), stats.data_ptr(), WS.get(256, x.device, slot=S2_CNT_SLOT).data_ptr(),
-             _stream())
-        return y, stats
-    if (SMALL_FUSE and SMALL_STATS and cout in (64, 128, 256) and _use_small(x.dtype, cin, cout, k, stride, (n, d, h, w_))
-            and not _use_conv1x1(x.dtype, cin, cout, k, n) and not _use_conv32(x.dtype, cin, cout, k, stride, n, w_)):
-        y = torch.empty((n, d, h, w_, cout), dtype=x.dtype, device=x.device)
-        stats = conv_small(0, x, cin, wpk, cout, gn, residual, y, want_stats=True)
-        if stats is not None:
-            return y, stats
-        return y, None
-    if (BRICK_STATS and cout % 32 == 0 and cin <= 256 and k == 3 and stride == 1
-            and _use_gen_brick(x.dtype, cin, cout, k, stride, (n, d, h, w_))
-            and not _use_conv1x1(x.dtype, cin, cout, k, n) and not _use_conv32(x.dtype, cin, cout, k, stride, n, w_)
-            and not _use_small(x.dtype, cin, cout, k, stride, (n, d, h, w_))
-            and get_option("CONVG_PERSIST") != 0):
-        # persistent brick conv with the output's GroupNorm(16) statistics from its epilogue (no statistics pass)
-        st, ga, be, G = gn if gn is not None else (None, None, None, 0)
-        y = torch.empty((n, d, h, w_, cout), dtype=x.dtype, device=x.device)
-        stats = torch.empty((n, 16, 2), dtype=torch.float32, device=x.device)
-        nws = query("u3d_convg_brick_stats_ws_floats", n, d, h, w_, cout)
-        ws = WS.get(4 * nws, x.device, slot=9)
-        if FUSED_FINALIZE:
-            call("u3d_convg_brick_stats_fused", x.data_ptr(), n, cin, d, h, w_, wpk.data_ptr(), cout, _ptr(st), _ptr(ga),
-                 _ptr(be), G, _ptr(residual), y.data_ptr(), ws.data_ptr(), nws, stats.data_ptr(),
-                 WS.get(256, x.device, slot=BRICK_CNT_SLOT).data_ptr(), _stream())
-        else:
-            call("u3d_convg_brick_stats", x.data_ptr(), n, cin, d, h, w_, wpk.data_ptr(), cout, _ptr(st), _ptr(ga),
-                 _ptr(be), G, _ptr(residual), y.data_ptr(), ws.data_ptr(), nws, stats.data_ptr(), _stream())
-        return y, stats
-    return conv_fwd(x, wpk, cout, k, stride, gn, residual), None
-
-
-# Work-stealing ring (u3d_conv32_ring_q): robust to a concurrent kernel holding CUs (a late workgroup's range is
-# taken over by the others instead of doubling the launch), but 10-25% slower alone (tools/concurrency.py,
-# profiles/r02_concurrency.json), and its GroupNorm backward takes the separate partial pass (another fp32 order
-# than the fused static ring). Used for the data-gradient ring only while COLLECTIVE_IN_FLIGHT is set;
-# U3D_RING_QUEUE=1 forces it for every ring launch.
-RING_QUEUE = os.environ.get("U3D_RING_QUEUE", "0") != "0"
-# The collective-tolerant forms (work-stealing data-gradient ring, short-range weight-gradient ring) are chosen
-# STATICALLY, never from a device poll, so a data-parallel step runs the same kernels and produces the same bits
-# every time. Default (DDP_TOLERANT off): the data-parallel backward runs exactly the plain step's forms, so an N-rank
-# step is bitwise the 1-rank step up to the all-reduce itself. U3D_DDP_TOLERANT=1: the tolerant forms from the first
-# bucket launch of a backward to its end (a latch in tape order: deterministic, but other fp32 sums than the plain
-# step's GroupNorm backward).
-DDP_TOLERANT = [os.environ.get("U3D_DDP_TOLERANT", "0") != "0"]
-COLLECTIVE_IN_FLIGHT = [False]  # the latch: set by u3d.ddp at a bucket launch when DDP_TOLERANT (tests may set it)
-
-
-def collective_in_flight():
-    """Whether the collective-tolerant kernel forms run now (a static latch, see DDP_TOLERANT)."""
-    return COLLECTIVE_IN_FLIGHT[0]
-
-
-def _ring_queue(dgrad=False):
-    return CONV32_FN == "u3d_conv32_ring" and (RING_QUEUE or (dgrad and collective_in_flight()))
-
-
-QUEUE_SLOT = 40  # workspace slot of the ring claim words (used by nothing else: the words must stay zero between launches)
-
-
-def _queue(device, shape):
-    """Zeroed claim words for the work-stealing ring kernels (left zero by every launch; one queue: launches are
-    stream-ordered on the caller's stream)."""
-    return WS.get(query("u3d_conv32_ring_q_queue_bytes", *shape), device, slot=QUEUE_SLOT).data_ptr()
-
-
-# the ring / persistent-brick conv epilogue statistics (and the ring data gradient's GroupNorm-backward coefficients)
-# finalized by the conv launch's last-arriving workgroup instead of a separate finalize launch (round 5, U3D_FUSED_FINALIZE=1).
-# Off by default: measured no cheaper than the launch it replaces (step A/B r05_e 5.671 / 5.672 off vs 5.687 / 5.678 on;
-# the in-step ring / brick launches grow 4-8 us each by the last arriver's drain + atomic + cross-XCD loads, r05_f trace)
-FUSED_FINALIZE = os.environ.get("U3D_FUSED_FINALIZE", "0") != "0"
-RING_CNT_SLOT, BRICK_CNT_SLOT, RING_GB_CNT_SLOT = 18, 19, 23
-# the 96^3 stride-2 3^3 forward (cin 32 -> cout 64, GN prologue) as an input-plane walk (conv_s2.hip, round 5);
-# U3D_S2_RING=0: the implicit GEMM + a statistics pass
-S2_RING = os.environ.get("U3D_S2_RING", "1") != "0"
-S2_SPART_SLOT, S2_CNT_SLOT = 21, 22
-SMALL_STATS = os.environ.get("U3D_SMALL_STATS", "1") != "0"  # GN(16) stats of conv_small outputs from its combine
-BRICK_STATS = os.environ.get("U3D_BRICK_STATS", "1") != "0"  # GN statistics from the persistent brick's epilogue
-RING_STATS = os.environ.get("U3D_RING_STATS", "1") != "0"  # GroupNorm statistics from the ring conv epilogue (False: separate u3d_gn_stats pass)
-SPLITK_WS_BYTES = 64 << 20
-# bench.py roofline: while PROBE is a list, every launch of the 96^3-class ring kernels (conv fwd / dgrad and the
-# stride-1 weight-gradient ring) records (start event, end event, label, flop, voxels) on the stream it runs on
-PROBE = None
-
-
-def _probe0():
-    if PROBE is None:
-        return None
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    return e0, e1
-
-
-def _probe1(p, label, flop, vox):
-    if p is not None:
-        p[1].record()
-        PROBE.append((p[0], p[1], label, flop, vox))
 USE_CONV32_BRICK = True
 CONV32_FN = "u3d_conv32_ring"   # "u3d_conv32_brick": the earlier halo-brick schedule (same results)
 
@@ -473,8 +271,8 @@ def _use_conv32(dtype, cin, cout, k, stride, n, w=32):
     return CONV32_FN == "u3d_conv32_ring" or (n <= 16 and w % 32 == 0)
 
 
-def _conv32_fits(x):
-    return CONV32_FN != "u3d_conv32_ring" or x.numel() * x.element_size() < (1 << 31)  # 32-bit buffer offsets
+def _conv32_fits(nbytes):
+    return CONV32_FN != "u3d_conv32_ring" or nbytes < (1 << 31)  # 32-bit buffer offsets
 
 
 USE_SMALL_CONV = True
@@ -502,110 +300,382 @@ def _use_gen_brick(dtype, cin, cout, k, stride, shape):
     return max(nb * max(1, -(-cout // 64)), nb * max(1, -(-cout // 32))) >= BRICK_MIN_WG
 
 
+USE_S2_BRICK = True  # stride-2 3^3 bf16 data gradient: one-launch parity-merged kernel (dgrad_s2.hip)
+ROUTES = ("conv1x1", "ring32", "s2", "small", "brick", "gemm")
+
+
+def conv_route(dtype, cx, cy, k, stride, shape, nbytes, dgrad=False, residual=None, bias=None, out_f32=False,
+               skip=None):
+    """The kernel family (one of ROUTES) the plain path runs for one conv and direction. conv_fwd reads x with cx
+    channels and produces cy; conv_dgrad (``dgrad``) reads dy with cx channels and produces dx with cy. shape =
+    (n, d, h, w) of the conv's input volume, nbytes = the size of the operand read. The precedence of the families is
+    written here and nowhere else. ``skip``: a family left out (what would run were it not there)."""
+    n, w_ = shape[0], shape[3]
+    plain = bias is None and not out_f32  # (a bias / fp32 output: the implicit GEMM's epilogue only)
+    if plain and residual is None and (stride == 1 or not dgrad) and _use_conv1x1(dtype, cx, cy, k, n):
+        return "conv1x1"  # (data gradient: dx = dy . W^T, the dgrad pack is [cin_p][cout_p])
+    if plain and skip != "ring32" and _use_conv32(dtype, cx, cy, k, stride, n, w_) and _conv32_fits(nbytes):
+        return "ring32"
+    if (dgrad and USE_S2_BRICK and dtype == torch.bfloat16 and k == 3 and stride == 2
+            and nbytes < (1 << 31) - 64):  # (its dy reads use 32-bit buffer offsets)
+        return "s2"
+    if plain and _use_small(dtype, cx, cy, k, stride, shape):
+        return "small"
+    if plain and _use_gen_brick(dtype, cx, cy, k, stride, shape):
+        return "brick"
+    return "gemm"
+
+
+def _route_fwd(x, cout, k, stride, residual=None, bias=None, out_f32=False):
+    return conv_route(x.dtype, x.shape[-1], cout, k, stride, tuple(x.shape[:4]), x.numel() * x.element_size(), False,
+                      residual, bias, out_f32)
+
+
+def _route_dgrad(dy, cin, in_shape, k, stride, skip=None):
+    return conv_route(dy.dtype, dy.shape[-1], cin, k, stride, tuple(in_shape), dy.numel() * dy.element_size(), True,
+                      skip=skip)
+
+
+# Work-stealing ring (u3d_conv32_ring_q): robust to a concurrent kernel holding CUs (a late workgroup's range is
+# taken over by the others instead of doubling the launch), but 10-25% slower alone (tools/concurrency.py,
+# profiles/r02_concurrency.json), and its GroupNorm backward takes the separate partial pass (another fp32 order
+# than the fused static ring). Used for the data-gradient ring only while COLLECTIVE_IN_FLIGHT is set;
+# U3D_RING_QUEUE=1 forces it for every ring launch.
+RING_QUEUE = os.environ.get("U3D_RING_QUEUE", "0") != "0"
+# The collective-tolerant forms (work-stealing data-gradient ring, short-range weight-gradient ring) are chosen
+# STATICALLY, never from a device poll, so a data-parallel step runs the same kernels and produces the same bits
+# every time. Default (DDP_TOLERANT off): the data-parallel backward runs exactly the plain step's forms, so an N-rank
+# step is bitwise the 1-rank step up to the all-reduce itself. U3D_DDP_TOLERANT=1: the tolerant forms from the first
+# bucket launch of a backward to its end (a latch in tape order: deterministic, but other fp32 sums than the plain
+# step's GroupNorm backward).
+DDP_TOLERANT = [os.environ.get("U3D_DDP_TOLERANT", "0") != "0"]
+COLLECTIVE_IN_FLIGHT = [False]  # the latch: set by u3d.ddp at a bucket launch when DDP_TOLERANT (tests may set it)
+
+
+def collective_in_flight():
+    """Whether the collective-tolerant kernel forms run now (a static latch, see DDP_TOLERANT)."""
+    return COLLECTIVE_IN_FLIGHT[0]
+
+
+def _ring_queue(dgrad=False):
+    return CONV32_FN == "u3d_conv32_ring" and (RING_QUEUE or (dgrad and collective_in_flight()))
+
+
+def _queue(device, shape):
+    """Zeroed claim words for the work-stealing ring kernels (left zero by every launch; one queue: launches are
+    stream-ordered on the caller's stream)."""
+    return WS.get(query("u3d_conv32_ring_q_queue_bytes", *shape), device, Slot.QUEUE).data_ptr()
+
+
+# the ring / persistent-brick conv epilogue statistics (and the ring data gradient's GroupNorm-backward coefficients)
+# finalized by the conv launch's last-arriving workgroup instead of a separate finalize launch (round 5, U3D_FUSED_FINALIZE=1).
+# Off by default: measured no cheaper than the launch it replaces (step A/B r05_e 5.671 / 5.672 off vs 5.687 / 5.678 on;
+# the in-step ring / brick launches grow 4-8 us each by the last arriver's drain + atomic + cross-XCD loads, r05_f trace)
+FUSED_FINALIZE = os.environ.get("U3D_FUSED_FINALIZE", "0") != "0"
+# the 96^3 stride-2 3^3 forward (cin 32 -> cout 64, GN prologue) as an input-plane walk (conv_s2.hip, round 5);
+# U3D_S2_RING=0: the implicit GEMM + a statistics pass
+S2_RING = os.environ.get("U3D_S2_RING", "1") != "0"
+SMALL_STATS = os.environ.get("U3D_SMALL_STATS", "1") != "0"  # GN(16) stats of conv_small outputs from its combine
+BRICK_STATS = os.environ.get("U3D_BRICK_STATS", "1") != "0"  # GN statistics from the persistent brick's epilogue
+RING_STATS = os.environ.get("U3D_RING_STATS", "1") != "0"  # GroupNorm statistics from the ring conv epilogue (False: separate u3d_gn_stats pass)
+# conv_small's split-K slabs combined inside its launch by each output tile's last-arriving workgroup (round 5,
+# u3d_conv_small2: no small_reduce_kernel launch); U3D_SMALL_FUSE=0: the two-kernel form
+SMALL_FUSE = os.environ.get("U3D_SMALL_FUSE", "1") != "0"
+# the forward ring stores relu(gn(x)) for the weight gradient (round 6; measured slower, off: the forward rings pay
+# +16-19 us per launch for the side stores, the GN-free weight gradient saves 7.5 us per launch; step 5.76 vs 5.62 ms)
+RING_XN = os.environ.get("U3D_RING_XN", "0") != "0"
+# stride-2 3^3 convs with cin >= 64 (the 48^3 / 24^3 / 12^3 downsampling convs on the implicit GEMM): normalise the
+# input once (round 6, kbench gpurun_out/r06_g: 48^3 forward 65.5 -> 48.4 + 14.1 us, its weight gradient 36.0 -> 30.2)
+S2_NORM_ONCE = os.environ.get("U3D_S2_NORM_ONCE", "1") != "0"
 GN_BWD_FUSED = os.environ.get("U3D_GN_BWD_FUSED", "1") != "0"  # GroupNorm-backward partials in the ring dgrad epilogue
-
-
-def conv_dgrad_gn(dy, wpk_dgrad, cin, x, k, stride, gn, dgb=None):
-    """Data gradient of conv(relu(gn(x))) with the GroupNorm backward's partial pass fused into the ring epilogue
-    (u3d_conv32_ring_dgrad_gn): returns (dA, parts) for gn_bwd_parts, or None where the static 32-channel ring does
-    not run this conv (the caller then takes conv_dgrad + gn_bwd). On the small-volume kernel (and with ``dgb``, a
-    callable returning the (dgamma, dbeta) destinations) the finalize runs inside the launch too: parts is then
-    ("coef", coef) for gn_bwd_apply_coef, dgamma / dbeta already written."""
-    n, d, h, w_ = x.shape[:4]
-    if not (GN_BWD_FUSED and gn is not None and dy.shape[-1] == 32 and _use_conv32(dy.dtype, cin, 32, k, stride, n, w_)
-            and CONV32_FN == "u3d_conv32_ring" and _conv32_fits(dy) and not _ring_queue(dgrad=True)):
-        if dgb is not None:
-            r = _conv_dgrad_gn_small(dy, wpk_dgrad, cin, x, k, stride, gn, dgb)
-            if r is not None:
-                return r
-        return _conv_dgrad_gn_brick(dy, wpk_dgrad, cin, x, k, stride, gn)
-    st, ga, be, G = gn
-    wps = query("u3d_conv32_ring_wps", n, d, h, w_)
-    da = torch.empty((n, d, h, w_, cin), dtype=dy.dtype, device=dy.device)
-    parts = torch.empty((n, wps, 32, 2), dtype=torch.float32, device=dy.device)
-    pr = _probe0()
-    if FUSED_FINALIZE and dgb is not None:  # the finalize by the launch's last-arriving workgroup (round 5)
-        dg, db = dgb()
-        coef = torch.empty((n, 5, 32), dtype=torch.float32, device=dy.device)
-        call("u3d_conv32_ring_dgrad_gn_fused", dy.data_ptr(), n, d, h, w_, wpk_dgrad.data_ptr(), x.data_ptr(),
-             st.data_ptr(), ga.data_ptr(), be.data_ptr(), G, da.data_ptr(), parts.data_ptr(), coef.data_ptr(), _ptr(dg),
-             _ptr(db), WS.get(256, dy.device, slot=RING_GB_CNT_SLOT).data_ptr(), _stream())
-        _probe1(pr, "conv32_ring dgrad +GN-bwd partials", 2.0 * n * d * h * w_ * 27 * 32 * 32, n * d * h * w_)
-        return da, ("coef", coef)
-    call("u3d_conv32_ring_dgrad_gn", dy.data_ptr(), n, d, h, w_, wpk_dgrad.data_ptr(), x.data_ptr(), st.data_ptr(),
-         ga.data_ptr(), be.data_ptr(), G, da.data_ptr(), parts.data_ptr(), _stream())
-    _probe1(pr, "conv32_ring dgrad +GN-bwd partials", 2.0 * n * d * h * w_ * 27 * 32 * 32, n * d * h * w_)
-    return da, parts
-
-
 GN_BWD_FUSED_BRICK = os.environ.get("U3D_GN_BWD_FUSED_BRICK", "1") != "0"  # the same in the persistent brick
 # ... up to this many voxels (n*d*h*w): the fused epilogue pays where the separate partial pass is latency-bound. Kernel
 # A/B (tools/kbench.py gnb*, gpurun_out/r04_g): 2x24^3 x 128 ch 51.4 -> 47.9 us for the data gradient + GN backward,
 # 2x48^3 x 64 ch 89.7 -> 92.5 us (the x loads and the epilogue sums outweigh the 56 MB partial pass there)
 GN_BWD_FUSED_BRICK_MAX_VOX = int(os.environ.get("U3D_GN_BWD_FUSED_BRICK_MAX_VOX", str(2 * 32 ** 3)))
-
-
 SMALL_GB = os.environ.get("U3D_SMALL_GB", "1") != "0"  # GN-backward partials + finalize in the small-volume dgrad
+SPLITK_WS_BYTES = 64 << 20
+# the implicit GEMM behind a GN prologue: up to this size (and from this many channels) relu(gn(x)) is materialised
+GN_MATERIALIZE_BYTES = 32 << 20
+GN_MATERIALIZE_MIN_C = 64
+# bench.py roofline: while PROBE is a list, every launch of the 96^3-class ring kernels (conv fwd / dgrad and the
+# stride-1 weight-gradient ring) records (start event, end event, label, flop, voxels) on the stream it runs on
+PROBE = None
 
 
-def _conv_dgrad_gn_small(dy, wpk_dgrad, cin, x, k, stride, gn, dgb):
-    """conv_dgrad_gn where conv_dgrad would run the small-volume kernel (u3d_conv_small_dgrad_gn): the partial pass and
-    the coefficient finalize inside the data-gradient launch; returns (dA, ("coef", coef)) or None."""
-    shape = tuple(x.shape[:4])
-    n, d, h, w_ = shape
-    cout = dy.shape[-1]
-    if not (GN_BWD_FUSED and SMALL_GB and SMALL_FUSE and dy.dtype == torch.bfloat16 and x.dtype == torch.bfloat16
-            and k == 3 and stride == 1 and _use_small(dy.dtype, cout, cin, k, stride, shape) and cin % 8 == 0
-            and n * cin * 2 <= 8192):
+def _probe0():
+    if PROBE is None:
         return None
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    return e0, e1
+
+
+def _probe1(p, label, shape, cin=32, cout=32):
+    """Closes _probe0 around a 3^3 ring launch (conv, or cin -> cout weight gradient) over shape = (n, d, h, w)."""
+    if p is not None:
+        p[1].record()
+        vox = shape[0] * shape[1] * shape[2] * shape[3]
+        PROBE.append((p[0], p[1], label, 2.0 * vox * 27 * cin * cout, vox))
+
+
+def _ring32(flip, src, shape, wpk, gn, residual, dst, q, label):
+    """The plain 32 -> 32 ring launch (forward, or ``flip``: data gradient); ``q``: its work-stealing form."""
+    st, ga, be, G = gn
+    args = (flip, src.data_ptr(), *shape, wpk.data_ptr(), _ptr(st), _ptr(ga), _ptr(be), G, _ptr(residual),
+            dst.data_ptr())
+    pr = _probe0()
+    if q:
+        call("u3d_conv32_ring_q", *args, None, _queue(src.device, shape), _stream())
+    else:
+        call(CONV32_FN, *args, _stream())
+    _probe1(pr, label, shape)
+
+
+def conv_fwd(x, wpk, cout, k, stride, gn=None, residual=None, bias=None, out_f32=False, route=None):
+    """x: [n,d,h,w,cin] -> [n,od,oh,ow,cout]. gn = (stats, gamma, beta, groups) fuses GroupNorm+ReLU. ``route``: the
+    conv's family where the caller has routed it already."""
+    require_device(x)
+    n, d, h, w_, cin = x.shape
+    route = route or _route_fwd(x, cout, k, stride, residual, bias, out_f32)
+    od, oh, ow = out_dim(d, k, stride), out_dim(h, k, stride), out_dim(w_, k, stride)
+    y = torch.empty((n, od, oh, ow, cout), dtype=torch.float32 if out_f32 else x.dtype, device=x.device)
+    st, ga, be, G = _gn4(gn)
+    if route == "conv1x1":
+        call("u3d_conv1x1", x.data_ptr(), n, cin, d, h, w_, wpk.data_ptr(), wpk.shape[-1], cout, stride, _ptr(st),
+             _ptr(ga), _ptr(be), G, y.data_ptr(), _stream())
+    elif route == "ring32":
+        _ring32(0, x, (n, d, h, w_), wpk, (st, ga, be, G), residual, y, _ring_queue(),
+                "conv32_ring fwd" + (" GN" if st is not None else "") + (" +res" if residual is not None else ""))
+    elif route == "small":
+        conv_small(0, x, cin, wpk, cout, (st, ga, be, G), residual, y)
+    elif route == "brick":
+        call("u3d_convg_brick", 0, x.data_ptr(), n, cin, d, h, w_, wpk.data_ptr(), cout, _ptr(st), _ptr(ga), _ptr(be),
+             G, _ptr(residual), y.data_ptr(), _stream())
+    else:
+        if (st is not None and x.dtype == torch.bfloat16 and cin >= GN_MATERIALIZE_MIN_C
+                and x.numel() * 2 <= GN_MATERIALIZE_BYTES):
+            # small deep-layer activation: materialise relu(gn(x)) once so the GEMM K loop has no GN arithmetic
+            x = gn_apply(x, st, ga, be, G)
+            st = ga = be = None
+            G = 0
+        ws = WS.get(SPLITK_WS_BYTES, x.device, Slot.SPLITK)
+        call("u3d_conv_fwd", dt_code(x.dtype), x.data_ptr(), n, cin, d, h, w_, wpk.data_ptr(), cout, k, stride,
+             _ptr(st), _ptr(ga), _ptr(be), G, _ptr(residual), _ptr(bias), y.data_ptr(), int(out_f32), ws.data_ptr(),
+             ws.numel(), _stream())
+    return y
+
+
+def conv_small(flip, x, cin, wpk, cout, gn, residual, y, want_stats=False):
+    """u3d_conv_small(2) into y; returns the output's GroupNorm(16) statistics [n,16,2] when want_stats and the launch
+    produced them (in-kernel combine with the contraction split), else None."""
+    n, d, h, w_ = x.shape[:4]
+    st, ga, be, G = _gn4(gn)
+    ws = WS.get(SPLITK_WS_BYTES, x.device, Slot.SPLITK)
+    args = (flip, x.data_ptr(), n, cin, d, h, w_, wpk.data_ptr(), cout, _ptr(st), _ptr(ga), _ptr(be), G, _ptr(residual),
+            y.data_ptr(), ws.data_ptr(), ws.numel())
+    if not SMALL_FUSE:
+        call("u3d_conv_small", *args, _stream())
+        return None
+    cnt = WS.get(query("u3d_conv_small_cnt_bytes", n, d, h, w_, cout), x.device, Slot.SMALL_CNT)
+    stats = sp = None
+    if want_stats:
+        stats = torch.empty((n, 16, 2), dtype=torch.float32, device=x.device)
+        sp = WS.get(4 * query("u3d_conv_small_spart_floats", n, d, h, w_), x.device, Slot.SMALL_SPART)
+    made = ctypes.c_int(0)
+    call("u3d_conv_small2", *args, cnt.data_ptr(), _ptr(sp), _ptr(stats), ctypes.addressof(made), _stream())
+    return stats if made.value else None
+
+
+def _ring_stats_ok(route, gn):
+    """The static ring's epilogue statistics: the ring32 family behind a GN prologue, and RING_STATS."""
+    return route == "ring32" and RING_STATS and gn is not None and CONV32_FN == "u3d_conv32_ring"
+
+
+def ring_xn_ok(x, cout, k, stride, gn):
+    """Whether conv_fwd_stats_xn applies: _ring_stats_ok, and RING_XN, neither the fused finalize nor the queue form."""
+    return (RING_XN and not FUSED_FINALIZE and not _ring_queue()
+            and _ring_stats_ok(_route_fwd(x, cout, k, stride), gn))
+
+
+def s2_normalise_once(x, cin, cout, k, stride, gn):
+    """Whether the tape materialises relu(gn(x)) for this conv: a stride-2 3^3 forward (always the gemm family) with
+    cin >= 64 (so never conv_fwd_stats' cin 32 stride-2 ring)."""
+    return (S2_NORM_ONCE and gn is not None and k == 3 and stride == 2 and x.dtype == torch.bfloat16 and cin >= 64
+            and cin % 8 == 0)
+
+
+def epilogue_stats_cout(cout):
+    """Whether the tape asks conv_fwd_stats for a conv behind a GN prologue that produces ``cout`` channels: the ring32
+    family produces 32, the brick's statistics form needs BRICK_STATS and cout % 32 == 0. A pre-filter, not a promise:
+    conv_fwd_stats decides. (Asked for every conv, its small and brick forms would also run without a GN prologue.)"""
+    return cout == 32 or (BRICK_STATS and cout % 32 == 0)
+
+
+def _ring_fwd_stats(x, wpk, gn, residual, want_xn=False):
+    """The 32 -> 32 ring forward behind a GN prologue with its output's GroupNorm(16) statistics from the epilogue:
+    (y, stats), or (y, stats, xn) on the static ring that also stores xn = relu(gn(x))."""
+    n, d, h, w_ = shape = tuple(x.shape[:4])
+    st, ga, be, G = gn
+    y = torch.empty((n, d, h, w_, 32), dtype=x.dtype, device=x.device)
+    stats = torch.empty((n, 16, 2), dtype=torch.float32, device=x.device)
+    q = not want_xn and _ring_queue()
+    nws = query("u3d_conv32_ring_q_stats_ws_floats", n, d, h, w_) if q else query("u3d_conv32_ring_stats_ws_floats", n)
+    ws = WS.get(4 * nws, x.device, Slot.CONV_STATS)
+    args = (x.data_ptr(), n, d, h, w_, wpk.data_ptr(), st.data_ptr(), ga.data_ptr(), be.data_ptr(), G, _ptr(residual),
+            y.data_ptr())
+    fused = FUSED_FINALIZE and not q and not want_xn  # finalized by the launch's last-arriving workgroup (round 5)
+    pr = _probe0()
+    if want_xn:
+        xn = torch.empty_like(x)
+        call("u3d_conv32_ring_stats_xn", *args, xn.data_ptr(), ws.data_ptr(), _stream())
+    elif q:
+        call("u3d_conv32_ring_q", 0, *args, ws.data_ptr(), _queue(x.device, shape), _stream())
+    elif fused:
+        call("u3d_conv32_ring_stats_fused", *args, ws.data_ptr(), stats.data_ptr(),
+             WS.get(256, x.device, Slot.RING_CNT).data_ptr(), _stream())
+    else:
+        call("u3d_conv32_ring_stats", *args, ws.data_ptr(), _stream())
+    _probe1(pr, "conv32_ring fwd GN" + (" +res" if residual is not None else "") + " +stats", shape)
+    if not fused:
+        fin = "u3d_conv32_ring_q_stats_finalize" if q else "u3d_conv32_ring_stats_finalize"
+        call(fin, ws.data_ptr(), n, d, h, w_, stats.data_ptr(), _stream())
+    return (y, stats, xn) if want_xn else (y, stats)
+
+
+def conv_fwd_stats_xn(x, wpk, cout, k, stride, gn, residual=None):
+    """conv_fwd_stats on the static ring that also returns xn = relu(gn(x)) (bf16 NDHWC, x's shape), stored by the
+    ring from its staged input: the conv's weight gradient then reads xn without a GroupNorm prologue (bitwise the
+    same partials as conv_wgrad(dy, x, ..., gn)). Caller checks ring_xn_ok. Returns (y, stats, xn)."""
+    return _ring_fwd_stats(x, wpk, gn, residual, want_xn=True)
+
+
+def conv_fwd_stats(x, wpk, cout, k, stride, gn=None, residual=None):
+    """conv_fwd that also returns the GroupNorm(16) statistics [n,16,2] of its output where a kernel family takes them
+    in its epilogue (the forms below, each an extension of one family); otherwise (conv_fwd(...), None)."""
+    n, d, h, w_, cin = x.shape
+    route = _route_fwd(x, cout, k, stride, residual)
+    if _ring_stats_ok(route, gn):
+        return _ring_fwd_stats(x, wpk, gn, residual)
+    if (route == "gemm" and S2_RING and gn is not None and residual is None and k == 3 and stride == 2
+            and x.dtype == torch.bfloat16 and cin == 32 and cout == 64
+            and query("u3d_conv_s2_ring_ok", n, cin, d, h, w_, cout)):
+        # stride-2 forward as an input-plane walk (reached only here): GN once per staged element, stats in-kernel
+        st, ga, be, G = gn
+        od, oh, ow = out_dim(d, 3, 2), out_dim(h, 3, 2), out_dim(w_, 3, 2)
+        y = torch.empty((n, od, oh, ow, cout), dtype=x.dtype, device=x.device)
+        stats = torch.empty((n, 16, 2), dtype=torch.float32, device=x.device)
+        sp = WS.get(4 * query("u3d_conv_s2_ring_ws_floats", n, d, h, w_), x.device, Slot.S2_SPART)
+        call("u3d_conv_s2_ring", x.data_ptr(), n, d, h, w_, wpk.data_ptr(), st.data_ptr(), ga.data_ptr(), be.data_ptr(),
+             G, y.data_ptr(), sp.data_ptr(), stats.data_ptr(), WS.get(256, x.device, Slot.S2_CNT).data_ptr(),
+             _stream())
+        return y, stats
+    if route == "small" and SMALL_FUSE and SMALL_STATS and cout in (64, 128, 256):  # (with or without a GN prologue)
+        y = torch.empty((n, d, h, w_, cout), dtype=x.dtype, device=x.device)
+        return y, conv_small(0, x, cin, wpk, cout, gn, residual, y, want_stats=True)
+    if (route == "brick" and BRICK_STATS and cout % 32 == 0 and cin <= 256
+            # (a 32 -> 32 operand past the ring's 2 GiB runs the plain brick: the statistics form never took those)
+            and (x.numel() * x.element_size() < (1 << 31)
+                 or conv_route(x.dtype, cin, cout, k, stride, (n, d, h, w_), 0) != "ring32")
+            and get_option("CONVG_PERSIST") != 0):
+        # persistent brick conv with the output's GroupNorm(16) statistics from its epilogue (no statistics pass)
+        st, ga, be, G = _gn4(gn)
+        y = torch.empty((n, d, h, w_, cout), dtype=x.dtype, device=x.device)
+        stats = torch.empty((n, 16, 2), dtype=torch.float32, device=x.device)
+        nws = query("u3d_convg_brick_stats_ws_floats", n, d, h, w_, cout)
+        ws = WS.get(4 * nws, x.device, Slot.CONV_STATS)
+        args = (x.data_ptr(), n, cin, d, h, w_, wpk.data_ptr(), cout, _ptr(st), _ptr(ga), _ptr(be), G, _ptr(residual),
+                y.data_ptr(), ws.data_ptr(), nws, stats.data_ptr())
+        if FUSED_FINALIZE:
+            call("u3d_convg_brick_stats_fused", *args, WS.get(256, x.device, Slot.BRICK_CNT).data_ptr(), _stream())
+        else:
+            call("u3d_convg_brick_stats", *args, _stream())
+        return y, stats
+    return conv_fwd(x, wpk, cout, k, stride, gn, residual, route=route), None
+
+
+def conv_dgrad_gn(dy, wpk_dgrad, cin, x, k, stride, gn, dgb=None):
+    """Data gradient of conv(relu(gn(x))) with the GroupNorm backward's partial pass fused into the ring epilogue
+    (u3d_conv32_ring_dgrad_gn): returns (dA, parts) for gn_bwd_parts, or None where no fused form runs this conv (the
+    caller then takes conv_dgrad + gn_bwd). On the small-volume kernel (and with ``dgb``, a callable returning the
+    (dgamma, dbeta) destinations) the finalize runs inside the launch too: parts is then ("coef", coef) for
+    gn_bwd_apply_coef, dgamma / dbeta already written."""
+    n, d, h, w_ = shape = tuple(x.shape[:4])
+    route = _route_dgrad(dy, cin, shape, k, stride)
+    if not (route == "ring32" and GN_BWD_FUSED and gn is not None and CONV32_FN == "u3d_conv32_ring"
+            and not _ring_queue(dgrad=True)):
+        # (where the ring runs without its own fused form, e.g. as the queue form under a collective, the small form
+        # still takes the volumes it would run were the ring not there; the brick form does not)
+        rs = route if route != "ring32" else _route_dgrad(dy, cin, shape, k, stride, skip="ring32")
+        r = None
+        if dgb is not None and _small_gb_ok(rs, x, cin):
+            ws = WS.get(SPLITK_WS_BYTES, dy.device, Slot.SPLITK)
+            r = _conv_dgrad_gn_small(dy, wpk_dgrad, cin, x, gn, dgb, ws)
+        return r if r is not None else _conv_dgrad_gn_brick(route, dy, wpk_dgrad, cin, x, gn)
+    st, ga, be, G = gn
+    wps = query("u3d_conv32_ring_wps", n, d, h, w_)
+    da = torch.empty((n, d, h, w_, cin), dtype=dy.dtype, device=dy.device)
+    parts = torch.empty((n, wps, 32, 2), dtype=torch.float32, device=dy.device)
+    args = (dy.data_ptr(), n, d, h, w_, wpk_dgrad.data_ptr(), x.data_ptr(), st.data_ptr(), ga.data_ptr(),
+            be.data_ptr(), G, da.data_ptr(), parts.data_ptr())
+    pr = _probe0()
+    if FUSED_FINALIZE and dgb is not None:  # the finalize by the launch's last-arriving workgroup (round 5)
+        dg, db = dgb()
+        coef = torch.empty((n, 5, 32), dtype=torch.float32, device=dy.device)
+        call("u3d_conv32_ring_dgrad_gn_fused", *args, coef.data_ptr(), _ptr(dg), _ptr(db),
+             WS.get(256, dy.device, Slot.RING_GB_CNT).data_ptr(), _stream())
+        parts = ("coef", coef)
+    else:
+        call("u3d_conv32_ring_dgrad_gn", *args, _stream())
+    _probe1(pr, "conv32_ring dgrad +GN-bwd partials", shape)
+    return da, parts
+
+
+def _small_gb_ok(route, x, cin):
+    """The small-volume data gradient with the GroupNorm backward's partial pass and finalize inside
+    (u3d_conv_small_dgrad_gn, and the backward pair built on it): the small family, and GN_BWD_FUSED, SMALL_GB,
+    SMALL_FUSE, a bf16 x and n * cin * 2 <= 8192."""
+    return (route == "small" and GN_BWD_FUSED and SMALL_GB and SMALL_FUSE and x.dtype == torch.bfloat16
+            and x.shape[0] * cin * 2 <= 8192)
+
+
+def _conv_dgrad_gn_small(dy, wpk_dgrad, cin, x, gn, dgb, ws, wgrad=()):
+    """The small family's data gradient with the GroupNorm backward inside (caller checks _small_gb_ok), alone
+    (u3d_conv_small_dgrad_gn) or, with wgrad = (ring, partials pointer, nsplit), as one launch with the weight gradient
+    (u3d_conv_small_bwd_pair). ws: the SPLITK slabs. Returns (dA, ("coef", coef)), or None: the launcher declined."""
+    n, d, h, w_ = x.shape[:4]
     st, ga, be, G = gn
     dg, db = dgb()
     da = torch.empty((n, d, h, w_, cin), dtype=dy.dtype, device=dy.device)
     coef = torch.empty((n, 5, cin), dtype=torch.float32, device=dy.device)
-    ws = WS.get(SPLITK_WS_BYTES, dy.device, slot=4)
-    cnt = WS.get(query("u3d_conv_small_cnt_bytes", n, d, h, w_, cin), dy.device, slot=SMALL_CNT_SLOT)
-    parts = WS.get(4 * query("u3d_conv_small_gb_parts_floats", n, d, h, w_, cin), dy.device, slot=SMALL_GB_SLOT)
+    cnt = WS.get(query("u3d_conv_small_cnt_bytes", n, d, h, w_, cin), dy.device, Slot.SMALL_CNT)
+    parts = WS.get(4 * query("u3d_conv_small_gb_parts_floats", n, d, h, w_, cin), dy.device, Slot.SMALL_GB)
     made = ctypes.c_int(0)
-    call("u3d_conv_small_dgrad_gn", dy.data_ptr(), n, cout, d, h, w_, wpk_dgrad.data_ptr(), cin, x.data_ptr(),
-         st.data_ptr(), ga.data_ptr(), be.data_ptr(), G, da.data_ptr(), ws.data_ptr(), ws.numel(), cnt.data_ptr(),
-         parts.data_ptr(), coef.data_ptr(), _ptr(dg), _ptr(db), ctypes.addressof(made), _stream())
-    if not made.value:
-        return None
-    return da, ("coef", coef)
-
-
-SMALL_GB_SLOT = 20
+    call("u3d_conv_small_bwd_pair" if wgrad else "u3d_conv_small_dgrad_gn", dy.data_ptr(), n, dy.shape[-1], d, h, w_,
+         wpk_dgrad.data_ptr(), cin, x.data_ptr(), st.data_ptr(), ga.data_ptr(), be.data_ptr(), G, da.data_ptr(),
+         ws.data_ptr(), ws.numel(), cnt.data_ptr(), parts.data_ptr(), coef.data_ptr(), _ptr(dg), _ptr(db), *wgrad,
+         ctypes.addressof(made), _stream())
+    return (da, ("coef", coef)) if made.value else None
 
 
 def gn_bwd_apply_coef(da, x, coef, groups, dx=None, accumulate=False):
     """The apply pass of the GroupNorm backward from precomputed coefficients (u3d_conv_small_dgrad_gn)."""
     n, c = x.shape[0], x.shape[-1]
     v = x.numel() // (n * c)
-    if dx is None:
-        dx = torch.empty_like(x)
-        accumulate = False
+    dx, accumulate = _dst(dx, accumulate, x)
     call("u3d_gn_bwd_apply_coef", da.data_ptr(), x.data_ptr(), n, c, v, groups, coef.data_ptr(), dx.data_ptr(),
          int(accumulate), _stream())
     return dx
 
 
-def _conv_dgrad_gn_brick(dy, wpk_dgrad, cin, x, k, stride, gn):
-    """conv_dgrad_gn where conv_dgrad would run the persistent brick (u3d_convg_brick_dgrad_gn): parts per brick."""
-    if not (GN_BWD_FUSED and GN_BWD_FUSED_BRICK and gn is not None and dy.dtype == torch.bfloat16):
-        return None
-    shape = tuple(x.shape[:4])
+def _conv_dgrad_gn_brick(route, dy, wpk_dgrad, cin, x, gn):
+    """conv_dgrad_gn on the brick family (u3d_convg_brick_dgrad_gn, parts per brick): with GN_BWD_FUSED_BRICK, up to
+    GN_BWD_FUSED_BRICK_MAX_VOX voxels and where the launcher has a partial layout for the shape."""
+    n, d, h, w_ = x.shape[:4]
     cout = dy.shape[-1]
-    n, d, h, w_ = shape
-    if n * d * h * w_ > GN_BWD_FUSED_BRICK_MAX_VOX:
-        return None
-    # only where conv_dgrad itself runs the generic brick (not the 32-channel ring, e.g. its queue form under a
-    # collective, nor the small-volume kernel)
-    if _use_conv32(dy.dtype, cin, cout, k, stride, n, w_) and _conv32_fits(dy):
-        return None
-    if _use_small(dy.dtype, cout, cin, k, stride, shape) or not _use_gen_brick(dy.dtype, cout, cin, k, stride, shape):
-        return None
-    nparts = query("u3d_convg_brick_gn_nparts", n, cin, d, h, w_, cout)
-    if nparts <= 0:
+    if not (route == "brick" and GN_BWD_FUSED and GN_BWD_FUSED_BRICK and gn is not None
+            and n * d * h * w_ <= GN_BWD_FUSED_BRICK_MAX_VOX
+            and (nparts := query("u3d_convg_brick_gn_nparts", n, cin, d, h, w_, cout)) > 0):
         return None
     st, ga, be, G = gn
     da = torch.empty((n, d, h, w_, cin), dtype=dy.dtype, device=dy.device)
@@ -615,41 +685,31 @@ def _conv_dgrad_gn_brick(dy, wpk_dgrad, cin, x, k, stride, gn):
     return da, parts
 
 
-def conv_dgrad(dy, wpk_dgrad, cin, in_shape, k, stride):
+def conv_dgrad(dy, wpk_dgrad, cin, in_shape, k, stride, route=None):
+    """dy [n,od,oh,ow,cout] -> dx [n,d,h,w,cin] (in_shape = (n, d, h, w)). ``route``: as in conv_fwd."""
     n, d, h, w_ = in_shape
     cout = dy.shape[-1]
+    route = route or _route_dgrad(dy, cin, in_shape, k, stride)
     dx = torch.empty((n, d, h, w_, cin), dtype=dy.dtype, device=dy.device)
-    if stride == 1 and _use_conv1x1(dy.dtype, cout, cin, k, n):  # dx = dy . W^T: the dgrad pack is [cin_p][cout_p]
+    if route == "conv1x1":
         call("u3d_conv1x1", dy.data_ptr(), n, cout, d, h, w_, wpk_dgrad.data_ptr(), wpk_dgrad.shape[-1], cin, 1, None,
              None, None, 0, dx.data_ptr(), _stream())
-        return dx
-    if _use_conv32(dy.dtype, cin, cout, k, stride, n, w_) and _conv32_fits(dy):
-        pr = _probe0()
+    elif route == "ring32":
         q = _ring_queue(dgrad=True)
-        if q:
-            call("u3d_conv32_ring_q", 1, dy.data_ptr(), n, d, h, w_, wpk_dgrad.data_ptr(), None, None, None, 0, None,
-                 dx.data_ptr(), None, _queue(dy.device, (n, d, h, w_)), _stream())
-        else:
-            call(CONV32_FN, 1, dy.data_ptr(), n, d, h, w_, wpk_dgrad.data_ptr(), None, None, None, 0, None,
-                 dx.data_ptr(), _stream())
-        _probe1(pr, "conv32_ring dgrad" + (" (work stealing)" if q else ""), 2.0 * n * d * h * w_ * 27 * 32 * 32,
-                n * d * h * w_)
-        return dx
-    if (USE_S2_BRICK and dy.dtype == torch.bfloat16 and k == 3 and stride == 2
-            and dy.numel() * dy.element_size() < (1 << 31) - 64):  # (its dy reads use 32-bit buffer offsets)
+        _ring32(1, dy, (n, d, h, w_), wpk_dgrad, _gn4(None), None, dx, q,
+                "conv32_ring dgrad" + (" (work stealing)" if q else ""))
+    elif route == "s2":
         call("u3d_conv_dgrad_s2", dy.data_ptr(), n, cout, wpk_dgrad.data_ptr(), cin, d, h, w_, dx.data_ptr(),
              _stream())
-        return dx
-    if _use_small(dy.dtype, cout, cin, k, stride, (n, d, h, w_)):
+    elif route == "small":
         conv_small(1, dy, cout, wpk_dgrad, cin, None, None, dx)
-        return dx
-    if _use_gen_brick(dy.dtype, cout, cin, k, stride, (n, d, h, w_)):
+    elif route == "brick":
         call("u3d_convg_brick", 1, dy.data_ptr(), n, cout, d, h, w_, wpk_dgrad.data_ptr(), cin, None, None, None, 0,
              None, dx.data_ptr(), _stream())
-        return dx
-    ws = WS.get(SPLITK_WS_BYTES, dy.device, slot=4)
-    call("u3d_conv_dgrad", dt_code(dy.dtype), dy.data_ptr(), n, cout, wpk_dgrad.data_ptr(), cin, d, h, w_, k, stride,
-         dx.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+    else:
+        ws = WS.get(SPLITK_WS_BYTES, dy.device, Slot.SPLITK)
+        call("u3d_conv_dgrad", dt_code(dy.dtype), dy.data_ptr(), n, cout, wpk_dgrad.data_ptr(), cin, d, h, w_, k,
+             stride, dx.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
     return dx
 
 
@@ -667,14 +727,17 @@ def s2_compact_ok(in_shape, cin, elsize):
     return d * h * w_ < (1 << 24) and n * cv * cin * elsize < (1 << 31)
 
 
+def s2_compact_dgrad_ok(dy, cin, in_shape):
+    """Whether conv_dgrad_1x1s2_compact serves a stride-2 1^3 conv's data gradient: S2_COMPACT, at the conv's output
+    resolution it is a stride-1 1^3 data gradient on the conv1x1 family, and s2_compact_ok's limits hold."""
+    return (S2_COMPACT and _route_dgrad(dy, cin, dy.shape[:4], 1, 1) == "conv1x1"
+            and s2_compact_ok(in_shape, cin, dy.element_size()))
+
+
 def conv_dgrad_1x1s2_compact(dy, wpk_dgrad, cin):
     """dx of a stride-2 1^3 conv at the conv's OUTPUT resolution (the values at the even input voxels; every
-    other input voxel's gradient is zero)."""
-    n, od, oh, ow, cout = dy.shape
-    dxc = torch.empty((n, od, oh, ow, cin), dtype=dy.dtype, device=dy.device)
-    call("u3d_conv1x1", dy.data_ptr(), n, cout, od, oh, ow, wpk_dgrad.data_ptr(), wpk_dgrad.shape[-1], cin, 1, None,
-         None, None, 0, dxc.data_ptr(), _stream())
-    return dxc
+    other input voxel's gradient is zero): there, a stride-1 1^3 data gradient."""
+    return conv_dgrad(dy, wpk_dgrad, cin, tuple(dy.shape[:4]), 1, 1, route="conv1x1")
 
 
 def expand_s2(dxc, in_shape):
@@ -688,7 +751,6 @@ def expand_s2(dxc, in_shape):
 USE_BRICK_WGRAD = True
 USE_RING_WGRAD = True      # stride-1 3^3 weight gradients: depth-streaming ring kernel (wgrad_ring.hip)
 RING_WGRAD_MIN_HW = 8      # h, w extents below this use the brick kernel (measured faster from 12^3 up)
-USE_S2_BRICK = True  # stride-2 3^3 bf16 data gradient: one-launch parity-merged kernel (dgrad_s2.hip)
 # stride-1 weight-gradient ring while a collective may hold CUs (or always with U3D_WGRAD_QUEUE=1): a grid of ~3x the
 # CUs in short plane ranges instead of one resident range per CU (each range keeps its own slab: same sums every run)
 WGRAD_QUEUE = os.environ.get("U3D_WGRAD_QUEUE", "0") != "0"
@@ -709,7 +771,7 @@ def conv_wgrad(dy, x, k, stride, gn=None, brick=None):
     """Returns (partials fp32 [nsplit, k^3, cout_p, cin_p], nsplit). bf16 3^3 convs use the halo-brick kernel."""
     n, d, h, w_, cin = x.shape
     cout = dy.shape[-1]
-    st, ga, be, G = gn if gn is not None else (None, None, None, 0)
+    st, ga, be, G = _gn4(gn)
     if brick is None:
         brick = _wgrad_route(dy, x, k, stride)
     if brick == "ring":
@@ -722,20 +784,14 @@ def conv_wgrad(dy, x, k, stride, gn=None, brick=None):
         pr = _probe0()
         call("u3d_conv_wgrad_ring", dy.data_ptr(), x.data_ptr(), n, cin, d, h, w_, cout, _ptr(st), _ptr(ga), _ptr(be),
              G, part.data_ptr(), ns, _stream())
-        _probe1(pr, f"wgrad_ring {cin}->{cout}" + (" GN" if st is not None else ""),
-                2.0 * n * d * h * w_ * 27 * cin * cout, n * d * h * w_)
+        _probe1(pr, f"wgrad_ring {cin}->{cout}" + (" GN" if st is not None else ""), (n, d, h, w_), cin, cout)
         return part, ns
-    if brick and k == 1:
-        ns = query("u3d_conv_wgrad1_splits", n, cin, d, h, w_, cout, stride)
-        part = torch.empty((ns, 1, round32(cout), round32(cin)), dtype=torch.float32, device=x.device)
-        call("u3d_conv_wgrad1", dy.data_ptr(), x.data_ptr(), n, cin, d, h, w_, cout, stride, _ptr(st), _ptr(ga),
-             _ptr(be), G, part.data_ptr(), ns, _stream())
-        return part, ns
-    if brick:
-        ns = query("u3d_conv_wgrad_brick_splits", n, cin, d, h, w_, cout, stride)
-        part = torch.empty((ns, 27, round32(cout), round32(cin)), dtype=torch.float32, device=x.device)
-        call("u3d_conv_wgrad_brick", dy.data_ptr(), x.data_ptr(), n, cin, d, h, w_, cout, stride, _ptr(st), _ptr(ga),
-             _ptr(be), G, part.data_ptr(), ns, _stream())
+    if brick:  # the 1^3 kernel, or halo bricks
+        fn, taps = ("u3d_conv_wgrad1", 1) if k == 1 else ("u3d_conv_wgrad_brick", 27)
+        ns = query(fn + "_splits", n, cin, d, h, w_, cout, stride)
+        part = torch.empty((ns, taps, round32(cout), round32(cin)), dtype=torch.float32, device=x.device)
+        call(fn, dy.data_ptr(), x.data_ptr(), n, cin, d, h, w_, cout, stride, _ptr(st), _ptr(ga), _ptr(be), G,
+             part.data_ptr(), ns, _stream())
         return part, ns
     ns = query("u3d_conv_wgrad_splits", n, cin, d, h, w_, cout, k, stride)
     part = torch.empty((ns, k ** 3, round32(cout), round32(cin)), dtype=torch.float32, device=x.device)
@@ -754,47 +810,29 @@ PAIR_CALLS = [0]  # launches of the pair (tests count them)
 
 def conv_bwd_pair_small(dy, pd, x, k, stride, gn, dgb):
     """conv_wgrad(dy, x, k, stride, gn) and conv_dgrad_gn(dy, pd, cin, x, k, stride, gn, dgb) in one launch where the
-    first runs the 12 x 12-tile ring or the 3 x 8 x 16 brick and the second the small-volume kernel with the finalize
-    inside: returns (part, ns, dA, ("coef", coef)), or None (nothing launched, no output touched: the caller takes
-    the two calls). Off while a collective is in flight: the DDP-tolerant weight gradient splits differently."""
-    if not (SMALL_BWD_PAIR and gn is not None and not collective_in_flight() and not WGRAD_QUEUE):
-        return None
-    if x.dim() != 5 or dy.dim() != 5:
+    first runs the 12 x 12-tile ring or the 3 x 8 x 16 brick and the second the small family with the finalize inside
+    (_small_gb_ok): returns (part, ns, dA, ("coef", coef)), or None (nothing launched, no output touched: the caller
+    takes the two calls). Off while a collective is in flight: the DDP-tolerant weight gradient splits differently."""
+    if not (SMALL_BWD_PAIR and gn is not None and not collective_in_flight() and not WGRAD_QUEUE
+            and x.dim() == 5 and dy.dim() == 5):
         return None
     n, d, h, w_, cin = x.shape
-    shape = (n, d, h, w_)
     cout = dy.shape[-1]
-    if not (GN_BWD_FUSED and SMALL_GB and SMALL_FUSE and dy.dtype == torch.bfloat16 and x.dtype == torch.bfloat16
-            and k == 3 and stride == 1 and _use_small(dy.dtype, cout, cin, k, stride, shape) and cin % 8 == 0
-            and n * cin * 2 <= 8192):
-        return None  # (_conv_dgrad_gn_small's conditions)
-    if _use_conv32(dy.dtype, cin, cout, k, stride, n, w_):
-        return None  # (conv_dgrad_gn takes the 32-channel ring first)
-    route = _wgrad_route(dy, x, k, stride)
-    if not route:
+    if not _small_gb_ok(_route_dgrad(dy, cin, (n, d, h, w_), k, stride), x, cin):
         return None
-    if os.environ.get("U3D_LIB") and not hasattr(_lib.lib(), "u3d_conv_small_bwd_pair"):
-        return None  # an A/B build of an older tree (_lib.lib)
-    ring = int(route == "ring")
-    ws = WS.get(SPLITK_WS_BYTES, dy.device, slot=4)
+    wroute = _wgrad_route(dy, x, k, stride)
+    if not wroute or (os.environ.get("U3D_LIB") and not hasattr(_lib.lib(), "u3d_conv_small_bwd_pair")):
+        return None  # (the latter: an A/B build of an older tree, _lib.lib)
+    ring = int(wroute == "ring")
+    ws = WS.get(SPLITK_WS_BYTES, dy.device, Slot.SPLITK)
     ns = query("u3d_conv_small_bwd_pair_ok", n, cout, d, h, w_, cin, ring, ws.numel())
     if ns <= 0:
         return None
-    st, ga, be, G = gn
-    dg, db = dgb()
-    da = torch.empty((n, d, h, w_, cin), dtype=dy.dtype, device=dy.device)
-    coef = torch.empty((n, 5, cin), dtype=torch.float32, device=dy.device)
     part = torch.empty((ns, 27, round32(cout), round32(cin)), dtype=torch.float32, device=x.device)
-    cnt = WS.get(query("u3d_conv_small_cnt_bytes", n, d, h, w_, cin), dy.device, slot=SMALL_CNT_SLOT)
-    parts = WS.get(4 * query("u3d_conv_small_gb_parts_floats", n, d, h, w_, cin), dy.device, slot=SMALL_GB_SLOT)
-    made = ctypes.c_int(0)
-    call("u3d_conv_small_bwd_pair", dy.data_ptr(), n, cout, d, h, w_, pd.data_ptr(), cin, x.data_ptr(),
-         st.data_ptr(), ga.data_ptr(), be.data_ptr(), G, da.data_ptr(), ws.data_ptr(), ws.numel(), cnt.data_ptr(),
-         parts.data_ptr(), coef.data_ptr(), _ptr(dg), _ptr(db), ring, part.data_ptr(), ns, ctypes.addressof(made),
-         _stream())
-    assert made.value, "u3d_conv_small_bwd_pair declined a shape u3d_conv_small_bwd_pair_ok accepted"
+    r = _conv_dgrad_gn_small(dy, pd, cin, x, gn, dgb, ws, (ring, part.data_ptr(), ns))
+    assert r is not None, "u3d_conv_small_bwd_pair declined a shape u3d_conv_small_bwd_pair_ok accepted"
     PAIR_CALLS[0] += 1
-    return part, ns, da, ("coef", coef)
+    return (part, ns) + r
 
 
 # sum each weight gradient's slabs right after the launch that wrote them (round 5, cache-resident) instead of in the
@@ -810,13 +848,18 @@ def sum_slabs(part, ns, cout, cin):
     return part, 1
 
 
+USE_HEAD = True
+# the partial-label loss hands its gradient to the streaming head unformed (loss.DeferredLossGrad) and the head's
+# backward forms it in registers (u3d_head_loss_bwd): no fp32 dlogits tensor
+HEAD_LOSS_FUSED = os.environ.get("U3D_HEAD_LOSS_FUSED", "1") != "0"
+HEAD_GN_PARTS = os.environ.get("U3D_HEAD_GN_PARTS", "1") == "1"
+HEAD_DBIAS_FUSED = os.environ.get("U3D_HEAD_DBIAS_FUSED", "1") == "1"  # 0: two channel-sum launches (A/B)
+
+
 def use_head(dtype, cin, cout, k, stride):
     """The streaming MFMA head kernel (head.hip) serves GN+ReLU + 1^3 conv with cout <= 32 (precls_conv)."""
     return USE_HEAD and dtype == torch.bfloat16 and k == 1 and stride == 1 and cout <= 32 and cin % 16 == 0 \
         and 16 <= cin <= 64
-
-
-USE_HEAD = True
 
 
 def head_fwd(x, wpk, cout, bias, gn):
@@ -824,7 +867,7 @@ def head_fwd(x, wpk, cout, bias, gn):
     n, cin = x.shape[0], x.shape[-1]
     v = x.numel() // (n * cin)
     y = torch.empty(tuple(x.shape[:-1]) + (cout,), dtype=torch.float32, device=x.device)
-    st, ga, be, G = gn if gn is not None else (None, None, None, 0)
+    st, ga, be, G = _gn4(gn)
     call("u3d_head_fwd", x.data_ptr(), n, v, cin, wpk.data_ptr(), cout, _ptr(bias), _ptr(st), _ptr(ga), _ptr(be), G,
          y.data_ptr(), _stream())
     return y
@@ -846,16 +889,6 @@ def head_bwd(dy, wpk_dgrad, cin, dbias=None):
     if dbias is not None:
         channel_sum(dbp, out=dbias)
     return dA, dyb
-
-
-# the partial-label loss hands its gradient to the streaming head unformed (loss.DeferredLossGrad) and the head's
-# backward forms it in registers (u3d_head_loss_bwd): no fp32 dlogits tensor
-HEAD_LOSS_FUSED = os.environ.get("U3D_HEAD_LOSS_FUSED", "1") != "0"
-
-
-HEAD_GN_PARTS = os.environ.get("U3D_HEAD_GN_PARTS", "1") == "1"
-HEAD_CNT_SLOT = 24  # the GN head backward's arrival counter (zeroed, left zeroed)
-HEAD_DBIAS_FUSED = os.environ.get("U3D_HEAD_DBIAS_FUSED", "1") == "1"  # 0: two channel-sum launches (A/B)
 
 
 def head_gn_parts_ok(lg, x0, cin, gn):
@@ -894,7 +927,7 @@ def head_loss_bwd(lg, lab, weights, sums, grad_out, wpk_dgrad, cin, dbias=None, 
         call("u3d_head_loss_bwd_gn", lg.data_ptr(), lab.data_ptr(), n, v, C, weights.data_ptr(), sums.data_ptr(),
              grad_out.data_ptr(), wpk_dgrad.data_ptr(), cin, dA.data_ptr(), dyb.data_ptr(), dbp.data_ptr(),
              x0.data_ptr(), st.data_ptr(), ga.data_ptr(), be.data_ptr(), G, parts.data_ptr(),
-             _ptr(dbias) if fused else None, _ptr(WS.get(256, lg.device, slot=HEAD_CNT_SLOT)) if fused else None,
+             _ptr(dbias) if fused else None, _ptr(WS.get(256, lg.device, Slot.HEAD_CNT)) if fused else None,
              _stream())
         if dbias is not None and not fused:
             channel_sum(dbp, out=dbias)
@@ -908,8 +941,8 @@ def head_loss_bwd(lg, lab, weights, sums, grad_out, wpk_dgrad, cin, dbias=None, 
     return dA, dyb
 
 
-STEM_SLOT = 13  # the conv1 kernel's fp32 weight table
 STEM_WS_BYTES = 27 * 32 * 4  # = u3d_stem_fwd_ws_bytes() (tests/test_host.py); a constant so A/B runs load older builds
+STEM_STATS = os.environ.get("U3D_STEM_STATS", "1") != "0"  # conv1's GroupNorm(16) statistics from its epilogue
 
 
 def stem_fwd(x_ncdhw, wpk, cout, stride, dtype):
@@ -917,34 +950,27 @@ def stem_fwd(x_ncdhw, wpk, cout, stride, dtype):
     n, cin, d, h, w_ = x_ncdhw.shape
     od, oh, ow = out_dim(d, 3, stride), out_dim(h, 3, stride), out_dim(w_, 3, stride)
     y = torch.empty((n, od, oh, ow, cout), dtype=dtype, device=x_ncdhw.device)
-    ws = WS.get(STEM_WS_BYTES, x_ncdhw.device, slot=STEM_SLOT)
+    ws = WS.get(STEM_WS_BYTES, x_ncdhw.device, Slot.STEM)
     call("u3d_stem_fwd", dt_code(dtype), x_ncdhw.data_ptr(), n, cin, d, h, w_, wpk.data_ptr(), cout, stride,
          y.data_ptr(), ws.data_ptr(), _stream())
     return y
-
-
-STEM_STATS = os.environ.get("U3D_STEM_STATS", "1") != "0"  # conv1's GroupNorm(16) statistics from its epilogue
 
 
 def stem_fwd_stats(x_ncdhw, wpk, cout, stride, dtype):
     """stem_fwd that also returns the output's GroupNorm(16) statistics [n,16,2] when the bf16 conv1 kernel runs with
     its epilogue statistics (u3d_stem1_fwd_stats); otherwise (stem_fwd(...), None)."""
     n, cin, d, h, w_ = x_ncdhw.shape
-    if STEM_STATS and dtype == torch.bfloat16 and cin == 1 and cout == 32 and stride == 1 and get_option("STEM1") != 0:
-        nws = query("u3d_stem1_stats_ws_floats", n, d, h, w_)
-        if nws > 0:
-            require_device(x_ncdhw)
-            y = torch.empty((n, d, h, w_, cout), dtype=dtype, device=x_ncdhw.device)
-            stats = torch.empty((n, 16, 2), dtype=torch.float32, device=x_ncdhw.device)
-            sp = WS.get(4 * nws, x_ncdhw.device, slot=STEM_STATS_SLOT)
-            ws = WS.get(STEM_WS_BYTES, x_ncdhw.device, slot=STEM_SLOT)
-            call("u3d_stem1_fwd_stats", x_ncdhw.data_ptr(), n, d, h, w_, wpk.data_ptr(), y.data_ptr(), ws.data_ptr(),
-                 sp.data_ptr(), stats.data_ptr(), _stream())
-            return y, stats
+    if (STEM_STATS and dtype == torch.bfloat16 and cin == 1 and cout == 32 and stride == 1 and get_option("STEM1") != 0
+            and (nws := query("u3d_stem1_stats_ws_floats", n, d, h, w_)) > 0):
+        require_device(x_ncdhw)
+        y = torch.empty((n, d, h, w_, cout), dtype=dtype, device=x_ncdhw.device)
+        stats = torch.empty((n, 16, 2), dtype=torch.float32, device=x_ncdhw.device)
+        sp = WS.get(4 * nws, x_ncdhw.device, Slot.STEM_STATS)
+        ws = WS.get(STEM_WS_BYTES, x_ncdhw.device, Slot.STEM)
+        call("u3d_stem1_fwd_stats", x_ncdhw.data_ptr(), n, d, h, w_, wpk.data_ptr(), y.data_ptr(), ws.data_ptr(),
+             sp.data_ptr(), stats.data_ptr(), _stream())
+        return y, stats
     return stem_fwd(x_ncdhw, wpk, cout, stride, dtype), None
-
-
-STEM_STATS_SLOT = 14
 
 
 def stem_wgrad(dy, x_ncdhw, stride):
@@ -959,7 +985,7 @@ def stem_wgrad(dy, x_ncdhw, stride):
 
 # ------------------------------------------------------------------------------------------ GroupNorm
 def _gn_ws(n, c, v, device):
-    return WS.get(query("u3d_gn_workspace_bytes", n, c, v), device, slot=1)
+    return WS.get(query("u3d_gn_workspace_bytes", n, c, v), device, Slot.GN)
 
 
 def gn_stats(x, groups):
@@ -969,10 +995,6 @@ def gn_stats(x, groups):
     call("u3d_gn_stats", dt_code(x.dtype), x.data_ptr(), n, c, v, groups, st.data_ptr(),
          _gn_ws(n, c, v, x.device).data_ptr(), _stream())
     return st
-
-
-GN_MATERIALIZE_BYTES = 32 << 20
-GN_MATERIALIZE_MIN_C = 64
 
 
 def gn_apply(x, stats, gamma, beta, groups):
@@ -988,9 +1010,7 @@ def gn_apply(x, stats, gamma, beta, groups):
 def gn_bwd(da, x, stats, gamma, beta, groups, dx=None, accumulate=False, dgamma=None, dbeta=None, acc_params=False):
     n, c = x.shape[0], x.shape[-1]
     v = x.numel() // (n * c)
-    if dx is None:
-        dx = torch.empty_like(x)
-        accumulate = False
+    dx, accumulate = _dst(dx, accumulate, x)
     call("u3d_gn_bwd", dt_code(x.dtype), da.data_ptr(), x.data_ptr(), n, c, v, groups, stats.data_ptr(),
          gamma.data_ptr(), beta.data_ptr(), dx.data_ptr(), int(accumulate), _ptr(dgamma), _ptr(dbeta), int(acc_params),
          _gn_ws(n, c, v, x.device).data_ptr(), _stream())
@@ -1002,9 +1022,7 @@ def gn_bwd_parts(da, x, parts, stats, gamma, beta, groups, dx=None, accumulate=F
     """gn_bwd from the per-workgroup partials of conv_dgrad_gn (no partial pass over da and x)."""
     n, c = x.shape[0], x.shape[-1]
     v = x.numel() // (n * c)
-    if dx is None:
-        dx = torch.empty_like(x)
-        accumulate = False
+    dx, accumulate = _dst(dx, accumulate, x)
     call("u3d_gn_bwd_parts", da.data_ptr(), x.data_ptr(), n, c, v, groups, stats.data_ptr(), gamma.data_ptr(),
          beta.data_ptr(), parts.data_ptr(), parts.shape[1], dx.data_ptr(), int(accumulate), _ptr(dgamma), _ptr(dbeta),
          int(acc_params), _gn_ws(n, c, v, x.device).data_ptr(), _stream())
@@ -1017,20 +1035,14 @@ def gn_bwd2(da1, da2, x, stats, gn1, gn2, groups, dx=None, accumulate=False, dpa
     da2_s2: da2 is a stride-2 1^3 conv's data gradient at that conv's output resolution (conv_dgrad_1x1s2_compact)."""
     n, c = x.shape[0], x.shape[-1]
     v = x.numel() // (n * c)
-    if dx is None:
-        dx = torch.empty_like(x)
-        accumulate = False
+    dx, accumulate = _dst(dx, accumulate, x)
+    fn, vol = "u3d_gn_bwd2", (v,)
     if da2_s2:
-        d, h, w_ = x.shape[1:4]
-        assert tuple(da2.shape) == (n, out_dim(d, 1, 2), out_dim(h, 1, 2), out_dim(w_, 1, 2), c), da2.shape
-        call("u3d_gn_bwd2_s2", dt_code(x.dtype), da1.data_ptr(), da2.data_ptr(), x.data_ptr(), n, c, d, h, w_, groups,
-             stats.data_ptr(), gn1[0].data_ptr(), gn1[1].data_ptr(), gn2[0].data_ptr(), gn2[1].data_ptr(),
-             dx.data_ptr(), int(accumulate), _ptr(dparams1[0]), _ptr(dparams1[1]), _ptr(dparams2[0]),
-             _ptr(dparams2[1]), 0, _gn_ws(n, c, v, x.device).data_ptr(), _stream())
-        return dx
-    call("u3d_gn_bwd2", dt_code(x.dtype), da1.data_ptr(), da2.data_ptr(), x.data_ptr(), n, c, v, groups,
-         stats.data_ptr(), gn1[0].data_ptr(), gn1[1].data_ptr(), gn2[0].data_ptr(), gn2[1].data_ptr(), dx.data_ptr(),
-         int(accumulate), _ptr(dparams1[0]), _ptr(dparams1[1]), _ptr(dparams2[0]), _ptr(dparams2[1]), 0,
+        fn, vol = "u3d_gn_bwd2_s2", tuple(x.shape[1:4])
+        assert tuple(da2.shape) == (n, *(out_dim(e, 1, 2) for e in vol), c), da2.shape
+    call(fn, dt_code(x.dtype), da1.data_ptr(), da2.data_ptr(), x.data_ptr(), n, c, *vol, groups, stats.data_ptr(),
+         gn1[0].data_ptr(), gn1[1].data_ptr(), gn2[0].data_ptr(), gn2[1].data_ptr(), dx.data_ptr(), int(accumulate),
+         _ptr(dparams1[0]), _ptr(dparams1[1]), _ptr(dparams2[0]), _ptr(dparams2[1]), 0,
          _gn_ws(n, c, v, x.device).data_ptr(), _stream())
     return dx
 
@@ -1053,19 +1065,15 @@ def upsample2x_add_stats(x, skip=None):
     """upsample2x_add that also returns the output's GroupNorm(16) statistics [n,16,2] from its epilogue (bf16,
     u3d_upsample2x_add_stats); otherwise (upsample2x_add(...), None)."""
     n, d, h, w_, c = x.shape
-    if UP_STATS and x.dtype == torch.bfloat16 and get_option("UP_QUAD") != 0:
-        nws = query("u3d_upsample2x_stats_ws_floats", n, c, d, h, w_)
-        if nws > 0:
-            y = torch.empty((n, 2 * d, 2 * h, 2 * w_, c), dtype=x.dtype, device=x.device)
-            stats = torch.empty((n, 16, 2), dtype=torch.float32, device=x.device)
-            sp = WS.get(4 * nws, x.device, slot=UP_STATS_SLOT)
-            call("u3d_upsample2x_add_stats", x.data_ptr(), n, c, d, h, w_, _ptr(skip), y.data_ptr(), sp.data_ptr(),
-                 stats.data_ptr(), _stream())
-            return y, stats
+    if (UP_STATS and x.dtype == torch.bfloat16 and get_option("UP_QUAD") != 0
+            and (nws := query("u3d_upsample2x_stats_ws_floats", n, c, d, h, w_)) > 0):
+        y = torch.empty((n, 2 * d, 2 * h, 2 * w_, c), dtype=x.dtype, device=x.device)
+        stats = torch.empty((n, 16, 2), dtype=torch.float32, device=x.device)
+        sp = WS.get(4 * nws, x.device, Slot.UP_STATS)
+        call("u3d_upsample2x_add_stats", x.data_ptr(), n, c, d, h, w_, _ptr(skip), y.data_ptr(), sp.data_ptr(),
+             stats.data_ptr(), _stream())
+        return y, stats
     return upsample2x_add(x, skip), None
-
-
-UP_STATS_SLOT = 15
 
 
 def upsample2x_bwd(dy, in_shape, dx=None, accumulate=False):
@@ -1101,7 +1109,7 @@ def channel_sum(x, out=None, accumulate=False):
     if out is None:
         out = torch.empty((c,), dtype=torch.float32, device=x.device)
         accumulate = False
-    ws = WS.get(query("u3d_channel_sum_workspace_bytes", rows, c), x.device, slot=2)
+    ws = WS.get(query("u3d_channel_sum_workspace_bytes", rows, c), x.device, Slot.CHANNEL_SUM)
     call("u3d_channel_sum", dt_code(x.dtype), x.data_ptr(), rows, c, out.data_ptr(), int(accumulate), ws.data_ptr(),
          _stream())
     return out
@@ -1132,7 +1140,7 @@ def partial_loss_fwd(logits, labels, weights, softmax=True, uce=True):
     V = logits.numel() // (S * C)
     sums = torch.empty((C, 4), dtype=torch.float64, device=logits.device)
     loss = torch.empty((1,), dtype=torch.float32, device=logits.device)
-    ws = WS.get(query("u3d_loss_workspace_bytes", S, V, C), logits.device, slot=3)
+    ws = WS.get(query("u3d_loss_workspace_bytes", S, V, C), logits.device, Slot.LOSS)
     call("u3d_partial_loss_fwd", logits.data_ptr(), labels.data_ptr(), S, V, C, int(softmax), weights.data_ptr(),
          int(uce), sums.data_ptr(), loss.data_ptr(), ws.data_ptr(), _stream())
     return loss, sums

@@ -145,23 +145,23 @@ class Tape:
         if gn_key is not None:
             gn = (self.stats(x, G), self.P[gn_key + ".weight"], self.P[gn_key + ".bias"], G)
         b = self.P[key + ".bias"] if bias else None
+        res = residual.t if residual is not None else None
         head = out_f32 and residual is None and ops.use_head(x.t.dtype, cin, cout, k, stride)
         st16 = None
         xn = None  # relu(gn(x)) stored by the forward ring: the weight gradient's operand (no GN prologue there)
         if head:  # precls_conv: streaming MFMA head (head.hip)
             y = ops.head_fwd(x.t, pf, cout, b, gn)
         elif self.record and b is None and not out_f32 and ops.ring_xn_ok(x.t, cout, k, stride, gn):
-            y, st16, xn = ops.conv_fwd_stats_xn(x.t, pf, cout, k, stride, gn,
-                                                residual.t if residual is not None else None)
+            y, st16, xn = ops.conv_fwd_stats_xn(x.t, pf, cout, k, stride, gn, res)
         elif b is None and not out_f32 and residual is None and ops.s2_normalise_once(x.t, cin, cout, k, stride, gn):
             # stride-2 3^3 conv on the implicit GEMM: relu(gn(x)) materialised once (the GEMM's prologue normalised
             # every gathered element, 27/8 times per input element) and reused by the weight gradient
             xn = ops.gn_apply(x.t, *gn)
             y, st16 = ops.conv_fwd_stats(xn, pf, cout, k, stride, None)
-        elif gn is not None and b is None and not out_f32 and (cout == 32 or (ops.BRICK_STATS and cout % 32 == 0)):
-            y, st16 = ops.conv_fwd_stats(x.t, pf, cout, k, stride, gn, residual.t if residual is not None else None)
+        elif gn is not None and b is None and not out_f32 and ops.epilogue_stats_cout(cout):
+            y, st16 = ops.conv_fwd_stats(x.t, pf, cout, k, stride, gn, res)
         else:
-            y = ops.conv_fwd(x.t, pf, cout, k, stride, gn, residual.t if residual is not None else None, b, out_f32)
+            y = ops.conv_fwd(x.t, pf, cout, k, stride, gn, res, b, out_f32)
         out = Act(y)
         if head and cout == 16:
             self.head_out = out  # the partial loss may hand its gradient to this head unformed (_TrunkFn)
@@ -198,11 +198,11 @@ class Tape:
                     if residual is not None:
                         self.acc_grad(residual, dy)
                     dyT = ops.cast(dy, self.dtype, pad_to=8)  # GEMM operand: channels padded to 8 (2-class head)
+                def dgb():  # the GroupNorm's parameter-gradient destinations, for a launch that writes them itself
+                    return self.grad_out(gn_key + ".weight", gn[1]), self.grad_out(gn_key + ".bias", gn[2])
                 paired = None  # weight gradient + data gradient (GN backward inside) in one launch: 12^3 / 6^3 levels
                 if xn is None and gn is not None and not head and pair is None:
-                    paired = ops.conv_bwd_pair_small(dyT, pd, x.t, k, stride, gn,
-                                                     dgb=lambda: (self.grad_out(gn_key + ".weight", gn[1]),
-                                                                  self.grad_out(gn_key + ".bias", gn[2])))
+                    paired = ops.conv_bwd_pair_small(dyT, pd, x.t, k, stride, gn, dgb)
                 if paired is not None:
                     part, ns, dA, parts = paired
                 elif xn is not None:
@@ -212,14 +212,11 @@ class Tape:
                 if ops.EAGER_SLAB_SUM and ns >= ops.EAGER_SLAB_MIN:
                     part, ns = ops.sum_slabs(part, ns, cout, cin)
                 self.pend_wgrad(part, ns, W, st, std, key + ".weight")
-                s2c = (gn is not None and pair == "park" and k == 1 and stride == 2 and ops.S2_COMPACT
-                       and ops._use_conv1x1(dyT.dtype, dyT.shape[-1], cin, 1, dyT.shape[0])
-                       and ops.s2_compact_ok(x.t.shape, cin, dyT.element_size()))
+                s2c = (gn is not None and pair == "park" and k == 1 and stride == 2
+                       and ops.s2_compact_dgrad_ok(dyT, cin, x.t.shape))
                 if paired is None and gn is not None and not head and pair != "park" \
                         and not (pair == "finish" and x.gn_pend):
-                    fused = ops.conv_dgrad_gn(dyT, pd, cin, x.t, k, stride, gn,  # GN-bwd partials in the epilogue
-                                              dgb=lambda: (self.grad_out(gn_key + ".weight", gn[1]),
-                                                           self.grad_out(gn_key + ".bias", gn[2])))
+                    fused = ops.conv_dgrad_gn(dyT, pd, cin, x.t, k, stride, gn, dgb)  # GN-bwd partials in the epilogue
                     if fused is not None:
                         dA, parts = fused
                 if parts is not None:
@@ -249,32 +246,26 @@ class Tape:
         return out
 
     def gn_bwd_one(self, x, dA, gn, gn_key, G, parts=None):
+        acc = dict(dx=x.grad, accumulate=x.grad is not None)
         if isinstance(parts, tuple) and parts[0] == "coef":  # partials, finalize and dgamma / dbeta done in the dgrad
-            x.grad = ops.gn_bwd_apply_coef(dA, x.t, parts[1], G, dx=x.grad, accumulate=x.grad is not None)
-            self.grad_done(gn_key + ".weight")
-            self.grad_done(gn_key + ".bias")
-            return
-        dg = self.grad_out(gn_key + ".weight", gn[1])
-        db = self.grad_out(gn_key + ".bias", gn[2])
-        if parts is not None:  # partial sums already taken by the data-gradient ring (ops.conv_dgrad_gn)
-            x.grad = ops.gn_bwd_parts(dA, x.t, parts, gn[0], gn[1], gn[2], G, dx=x.grad,
-                                      accumulate=x.grad is not None, dgamma=dg, dbeta=db)
+            x.grad = ops.gn_bwd_apply_coef(dA, x.t, parts[1], G, **acc)
         else:
-            x.grad = ops.gn_bwd(dA, x.t, gn[0], gn[1], gn[2], G, dx=x.grad,
-                                accumulate=x.grad is not None, dgamma=dg, dbeta=db)
+            acc.update(dgamma=self.grad_out(gn_key + ".weight", gn[1]), dbeta=self.grad_out(gn_key + ".bias", gn[2]))
+            if parts is not None:  # partial sums already taken by the data-gradient ring (ops.conv_dgrad_gn)
+                x.grad = ops.gn_bwd_parts(dA, x.t, parts, gn[0], gn[1], gn[2], G, **acc)
+            else:
+                x.grad = ops.gn_bwd(dA, x.t, gn[0], gn[1], gn[2], G, **acc)
         self.grad_done(gn_key + ".weight")
         self.grad_done(gn_key + ".bias")
 
     def up_add(self, x, skip, stats=False):
         """upsamplex2 (trilinear, align_corners=False) + skip, unet3D.py:1646 / :1764-1783. ``stats``: the output feeds
         GroupNorm(16)s (a decoder block): take its statistics from the upsample's epilogue."""
-        if stats:
-            y, st16 = ops.upsample2x_add_stats(x.t, skip.t if skip is not None else None)
-            out = Act(y)
-            if st16 is not None:
-                out.stats[16] = st16
-        else:
-            out = Act(ops.upsample2x_add(x.t, skip.t if skip is not None else None))
+        sk = skip.t if skip is not None else None
+        y, st16 = ops.upsample2x_add_stats(x.t, sk) if stats else (ops.upsample2x_add(x.t, sk), None)
+        out = Act(y)
+        if st16 is not None:
+            out.stats[16] = st16
         if self.record:
             def bwd():
                 dy = out.grad
