@@ -109,7 +109,10 @@ int u3d_conv_fwd(int dtype, const void* x, int n, int cin, int d, int h, int w, 
 int u3d_conv_dgrad(int dtype, const void* dy, int n, int cout, const void* wpk_dgrad, int cin, int d, int h,
                    int w, int ksize, int stride, void* dx, float* ws, long long ws_bytes, u3d_stream_t stream);
 /* Weight gradient partial slabs: partials[s][t][co][ci] = sum over voxel split s of dy * A, with
- * A = relu(gn(x)) recomputed in the prologue (same gn_* as the forward call). */
+ * A = relu(gn(x)) recomputed in the prologue (same gn_* as the forward call). Every entry of every slab is
+ * written; the rows co >= cout and the columns ci >= cin of the cout_p / cin_p padding hold exact zeros (the
+ * prologue is not applied to padding channels). u3d_conv_wgrad_ring, _brick and u3d_conv_wgrad1 keep the same
+ * contract. */
 int u3d_conv_wgrad_splits(int n, int cin, int d, int h, int w, int cout, int ksize, int stride);
 int u3d_conv_wgrad(int dtype, const void* dy, const void* x, int n, int cin, int d, int h, int w, int cout,
                    int ksize, int stride, const float* gn_stats, const float* gn_gamma, const float* gn_beta,

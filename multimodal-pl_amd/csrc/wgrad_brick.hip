@@ -141,6 +141,10 @@ __global__ __launch_bounds__(512, 1) void wgrad1_kernel(const bf16* __restrict__
         if (pn[i] != gn_n) {
           gn_n = pn[i];
           gn_coef8(gstat, gamma, beta, g.gn_groups, g.cin, gn_n, ci0 + ch * 8, sc, sh);
+          if (ci0 + ch * 8 >= g.cin) {  // a chunk of the cin_p padding (gn_coef8 clamps to channel cin - 1): stays zero
+#pragma unroll
+            for (int k = 0; k < 4; ++k) sc[k] = sh[k] = f32x2{0.f, 0.f};
+          }
         }
         a = gn_relu8(a, sc, sh);
       }

@@ -193,10 +193,13 @@ __device__ __forceinline__ void wgrad_brick_body(char* const lds, const int wg, 
       if (tid < 4) {
         f32x2 sc[4], sh[4];
         gn_coef8(gstat, gamma, beta, g.gn_groups, g.cin, n, ci0 + tid * 8, sc, sh);
+        // a chunk past cin (cin_p padding) holds zeros and must stay zero: gn_coef8 clamps to channel cin - 1, whose
+        // relu(sh) > 0 would put sum(dy) * relu(sh) into the slab's padded ci columns
+        const bool pad = ci0 + tid * 8 >= g.cin;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-          gsc[tid][k] = sc[k];
-          gsh[tid][k] = sh[k];
+          gsc[tid][k] = pad ? f32x2{0.f, 0.f} : sc[k];
+          gsh[tid][k] = pad ? f32x2{0.f, 0.f} : sh[k];
         }
       }
       __syncthreads();
