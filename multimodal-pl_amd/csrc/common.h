@@ -447,5 +447,7 @@ __device__ __forceinline__ TileSplit xcd_tile_split() {
 
 __host__ __device__ inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 __host__ __device__ inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
+// an operand of `bytes` bytes is addressable by a buffer descriptor's 32-bit offsets (a 64-B access stays below 2 GiB)
+inline bool fits_buffer_offsets(long long bytes) { return bytes < (1LL << 31) - 64; }
 
 }  // namespace u3d

@@ -768,6 +768,27 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(Geom g, const T* __r
   }
 }
 
+// the bf16 kernel's launch for one (BM, BN, WM, WN) tile shape, at KC = 8 (64-channel K stages) or 4
+template <typename TO>
+struct IgemmArgs {
+  const bf16 *x, *wpk;
+  TO* y;
+  const bf16* res;
+  const float *bias, *st, *ga, *be;
+  hipStream_t s;
+};
+
+template <typename TO, int BM, int BN, int WM, int WN>
+static void launch_igemm_bf16(const Geom& g, const IgemmArgs<TO>& a) {
+  const dim3 grid(g.mtiles * g.ntiles * g.nsamp * g.nsplit);
+  if (g.cin_p % 64 == 0)
+    hipLaunchKernelGGL((igemm_bf16_kernel<TO, BM, BN, WM, WN, 8>), grid, dim3(NTHR), 0, a.s, a.x, a.wpk, a.y, a.res,
+                       a.bias, a.st, a.ga, a.be, g);
+  else
+    hipLaunchKernelGGL((igemm_bf16_kernel<TO, BM, BN, WM, WN, 4>), grid, dim3(NTHR), 0, a.s, a.x, a.wpk, a.y, a.res,
+                       a.bias, a.st, a.ga, a.be, g);
+}
+
 template <typename T, typename TO>
 static int launch_igemm(Geom g, int n, const T* x, const T* wpk, TO* y, const T* res, const float* bias,
                         const float* st, const float* ga, const float* be, float* ws, long long ws_bytes,
@@ -812,37 +833,11 @@ static int launch_igemm(Geom g, int n, const T* x, const T* wpk, TO* y, const T*
       g.kps = (g.ntaps * (g.cin_p / 64) + ns - 1) / ns;
       g.nsplit = ns = std::min(ns, g.ntaps * (g.cin_p / 64));
     }
-    dim3 grid(g.mtiles * g.ntiles * n * ns);
-    const bool k64 = g.cin_p % 64 == 0;
-    if (BN == 32) {
-      if (k64)
-        hipLaunchKernelGGL((igemm_bf16_kernel<TO, 128, 32, 4, 1, 8>), grid, dim3(NTHR), 0, s, x, wpk, y, res, bias, st,
-                           ga, be, g);
-      else
-        hipLaunchKernelGGL((igemm_bf16_kernel<TO, 128, 32, 4, 1, 4>), grid, dim3(NTHR), 0, s, x, wpk, y, res, bias, st,
-                           ga, be, g);
-    } else if (BN == 64 && bm256) {
-      if (k64)
-        hipLaunchKernelGGL((igemm_bf16_kernel<TO, 256, 64, 2, 2, 8>), grid, dim3(NTHR), 0, s, x, wpk, y, res, bias, st,
-                           ga, be, g);
-      else
-        hipLaunchKernelGGL((igemm_bf16_kernel<TO, 256, 64, 2, 2, 4>), grid, dim3(NTHR), 0, s, x, wpk, y, res, bias, st,
-                           ga, be, g);
-    } else if (BN == 64) {
-      if (k64)
-        hipLaunchKernelGGL((igemm_bf16_kernel<TO, 128, 64, 2, 2, 8>), grid, dim3(NTHR), 0, s, x, wpk, y, res, bias, st,
-                           ga, be, g);
-      else
-        hipLaunchKernelGGL((igemm_bf16_kernel<TO, 128, 64, 2, 2, 4>), grid, dim3(NTHR), 0, s, x, wpk, y, res, bias, st,
-                           ga, be, g);
-    } else {
-      if (k64)
-        hipLaunchKernelGGL((igemm_bf16_kernel<TO, 128, 128, 2, 2, 8>), grid, dim3(NTHR), 0, s, x, wpk, y, res, bias,
-                           st, ga, be, g);
-      else
-        hipLaunchKernelGGL((igemm_bf16_kernel<TO, 128, 128, 2, 2, 4>), grid, dim3(NTHR), 0, s, x, wpk, y, res, bias,
-                           st, ga, be, g);
-    }
+    const IgemmArgs<TO> a{x, wpk, y, res, bias, st, ga, be, s};
+    if (BN == 32) launch_igemm_bf16<TO, 128, 32, 4, 1>(g, a);
+    else if (BN == 64 && bm256) launch_igemm_bf16<TO, 256, 64, 2, 2>(g, a);
+    else if (BN == 64) launch_igemm_bf16<TO, 128, 64, 2, 2>(g, a);
+    else launch_igemm_bf16<TO, 128, 128, 2, 2>(g, a);
   } else if (BN == 32) {
     dim3 grid(cdiv(Mq, 128), cdiv(g.cout, 32), n * ns);
     hipLaunchKernelGGL((igemm_kernel<T, TO, 128, 32, 4, 1>), grid, dim3(NTHR), 0, s, x, wpk, y, res, bias, st, ga,
@@ -862,6 +857,20 @@ static int launch_igemm(Geom g, int n, const T* x, const T* wpk, TO* y, const T*
 
 static int out_dim(int d, int k, int s) { return (d + 2 * (k / 2) - k) / s + 1; }
 
+// The Geom fields the entry points share: channels (and their 32-padded counts), the input grid and the output grid
+// of a ksize^3 conv at `stride` over it, every output voxel a GEMM row (q = o). Taps, gn_groups and the launch's
+// split / tile fields are the caller's and launch_igemm's.
+static Geom igemm_geom(int cin, int cout, int d, int h, int w, int ksize, int stride) {
+  Geom g{};
+  g.cin = cin; g.cout = cout; g.cin_p = round_up(cin, 32); g.cout_p = round_up(cout, 32);
+  g.id = d; g.ih = h; g.iw = w;
+  g.od = g.qd = out_dim(d, ksize, stride);
+  g.oh = g.qh = out_dim(h, ksize, stride);
+  g.ow = g.qw = out_dim(w, ksize, stride);
+  g.so = 1; g.si = stride;
+  return g;
+}
+
 }  // namespace u3d
 
 using namespace u3d;
@@ -879,16 +888,7 @@ extern "C" int u3d_conv_fwd(int dtype, const void* x, int n, int cin, int d, int
   U3D_REQUIRE(!gn_stats || (gn_gamma && gn_beta && gn_groups > 0 && cin % gn_groups == 0 && cin <= 256),
               "conv_fwd: bad GroupNorm prologue (groups %d, cin %d)", gn_groups, cin);
   U3D_REQUIRE(!(y_f32 && residual), "conv_fwd: residual with fp32 output unsupported");
-  Geom g{};
-  g.cin = cin;
-  g.cout = cout;
-  g.cin_p = round_up(cin, 32);
-  g.cout_p = round_up(cout, 32);
-  g.id = d; g.ih = h; g.iw = w;
-  g.od = out_dim(d, ksize, stride); g.oh = out_dim(h, ksize, stride); g.ow = out_dim(w, ksize, stride);
-  g.qd = g.od; g.qh = g.oh; g.qw = g.ow;
-  g.so = 1; g.pod = g.poh = g.pow_ = 0;
-  g.si = stride;
+  Geom g = igemm_geom(cin, cout, d, h, w, ksize, stride);
   g.gn_groups = gn_groups;
   fill_taps(g, ksize, false);
   hipStream_t s = (hipStream_t)stream;
@@ -913,15 +913,12 @@ extern "C" int u3d_conv_dgrad(int dtype, const void* dy, int n, int cout, const 
   U3D_REQUIRE(dy && wpk_dgrad && dx, "conv_dgrad: null pointer");
   U3D_REQUIRE(stride == 1 || (d % 2 == 0 && h % 2 == 0 && w % 2 == 0), "conv_dgrad: stride 2 needs even dims");
   hipStream_t s = (hipStream_t)stream;
-  Geom g{};
-  g.cin = cout;  // contraction over the forward's output channels
-  g.cout = cin;
-  g.cin_p = round_up(cout, 32);
-  g.cout_p = round_up(cin, 32);
-  g.od = d; g.oh = h; g.ow = w;
-  const int od = out_dim(d, ksize, stride), oh = out_dim(h, ksize, stride), ow = out_dim(w, ksize, stride);
-  g.id = od; g.ih = oh; g.iw = ow;
-  g.gn_groups = 0;
+  // the forward's geometry with the roles swapped: contraction over the forward's output channels, dy (on the
+  // forward's output grid) is read and dx written; a stride-2 launch covers one parity class of dx (q = x / 2)
+  Geom g = igemm_geom(cout, cin, d, h, w, ksize, stride);
+  std::swap(g.id, g.od); std::swap(g.ih, g.oh); std::swap(g.iw, g.ow);
+  g.qd = d / stride; g.qh = h / stride; g.qw = w / stride;
+  g.so = stride; g.si = 1;
   auto run = [&](const Geom& gg) -> int {
     if (dtype == U3D_BF16)
       return launch_igemm<bf16, bf16>(gg, n, (const bf16*)dy, (const bf16*)wpk_dgrad, (bf16*)dx, nullptr, nullptr,
@@ -930,8 +927,6 @@ extern "C" int u3d_conv_dgrad(int dtype, const void* dy, int n, int cout, const 
                                       nullptr, nullptr, nullptr, ws, ws_bytes, s);
   };
   if (stride == 1) {
-    g.qd = d; g.qh = h; g.qw = w;
-    g.so = 1; g.si = 1;
     fill_taps(g, ksize, true);
     return run(g);
   }
@@ -940,8 +935,6 @@ extern "C" int u3d_conv_dgrad(int dtype, const void* dy, int n, int cout, const 
   // ksize 1 (pad 0): only the even-parity class gets a contribution; the rest is zero (a streaming memset is as
   // fast as any fused zero-fill: writing the zeros from the GEMM epilogue measured 2.3x slower)
   if (ksize == 1) U3D_HIP(hipMemsetAsync(dx, 0, (size_t)n * d * h * w * cin * (dtype == U3D_BF16 ? 2 : 4), s));
-  g.so = 2; g.si = 1;
-  g.qd = d / 2; g.qh = h / 2; g.qw = w / 2;
   for (int pd = 0; pd < 2; ++pd)
     for (int ph = 0; ph < 2; ++ph)
       for (int pw = 0; pw < 2; ++pw) {
@@ -998,16 +991,7 @@ extern "C" int u3d_conv_wgrad(int dtype, const void* dy, const void* x, int n, i
   U3D_REQUIRE(nsplit >= 1, "conv_wgrad: nsplit");
   U3D_REQUIRE(!gn_stats || (gn_gamma && gn_beta && gn_groups > 0 && cin % gn_groups == 0 && cin <= 256),
               "conv_wgrad: bad GroupNorm prologue");
-  Geom g{};
-  g.cin = cin;
-  g.cout = cout;
-  g.cin_p = round_up(cin, 32);
-  g.cout_p = round_up(cout, 32);
-  g.id = d; g.ih = h; g.iw = w;
-  g.od = g.qd = out_dim(d, ksize, stride);
-  g.oh = g.qh = out_dim(h, ksize, stride);
-  g.ow = g.qw = out_dim(w, ksize, stride);
-  g.so = 1; g.si = stride;
+  Geom g = igemm_geom(cin, cout, d, h, w, ksize, stride);
   g.gn_groups = gn_groups;
   fill_taps(g, ksize, false);
   const long long M = (long long)n * g.qd * g.qh * g.qw;

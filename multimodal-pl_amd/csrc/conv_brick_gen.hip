@@ -899,6 +899,86 @@ static bool pbrick_bw8(int w) {
   return e8 >= 0 ? e8 != 0 : (w % 16 != 0 && w % 8 == 0);
 }
 
+// 64-channel co tiles, unless they give fewer than 128 workgroups and 32-channel tiles give at least 128 (the 24^3 x
+// 64-channel decoder convs: 72 -> 144 workgroups, fwd 49 -> 25 us, dgrad 40 -> 20 us). Not below that: at 24^3 x 128
+// channels (144 workgroups with 64-channel tiles) 32-channel tiles measured slower (63.5 -> 78.7 us).
+// U3D_CONVG_CO32 = 0 / 1 forces the choice (experiments).
+static bool gb_co64(long long units, int cout, int cout_p) {
+  const int env_co32 = opt(OPT_CONVG_CO32);
+  if (cout_p < 64 || env_co32 == 1) return false;
+  return !(env_co32 < 0 && units * cdiv(cout, 64) < 128 && units * cdiv(cout, 32) >= 128);
+}
+
+struct GBPlan {
+  bool pers, bw8, co64;  // the persistent form, its 8-wide bricks, 64-channel co tiles
+  int nunits, per, nwg;  // (brick, co tile) units, units per workgroup (1 in the one-shot form), workgroups
+};
+
+// The launch plan of the generic brick conv: which form runs, brick width and co tile, and the grid. Fills g's shape
+// fields for the chosen form (nbw and nct depend on it). The launcher and u3d_convg_brick_gn_nparts both plan here, so
+// `parts` is never laid out for another form than the one that writes it. cin / cout are the launch's own (a data
+// gradient contracts over cin = the forward's cout); gn: a GroupNorm prologue (or, with gbparts, the fused backward).
+static GBPlan gb_plan(bool flip, int n, int cin, int d, int h, int w, int cout, bool gn, bool residual, bool gbparts,
+                      GBGeom& g) {
+  g = GBGeom{};
+  g.n = n; g.d = d; g.h = h; g.w = w;
+  g.cin = cin; g.cout = cout; g.cin_p = round_up(cin, 32); g.cout_p = round_up(cout, 32);
+  GBPlan p{};
+  // the persistent form runs unless CONVG_PERSIST = 0 (the one-shot kernel; u3d_set_option lets a test compare both
+  // in-process), x or the weight pack is beyond its 32-bit buffer offsets, the GroupNorm has more than GB_MAXC
+  // channels, or a data gradient adds a residual (not a trunk routing, kept for the ABI: the persistent data gradient
+  // has no residual path, so its epilogue reserves no registers for one)
+  p.pers = opt(OPT_CONVG_PERSIST) != 0 && n >= 1 && n <= GB_MAXN &&
+           fits_buffer_offsets((long long)n * d * h * w * std::max(cin, cout) * 2) &&
+           fits_buffer_offsets(27LL * g.cout_p * g.cin_p * 2) &&
+           (!gn || (gbparts ? g.cout_p : g.cin_p) <= GB_MAXC) && !(flip && residual);
+  p.bw8 = p.pers && pbrick_bw8(w);
+  g.nbd = cdiv(d, GB_BD); g.nbh = cdiv(h, GB_BH); g.nbw = cdiv(w, p.bw8 ? 8 : GB_BW);
+  const long long bricks = (long long)n * g.nbd * g.nbh * g.nbw;
+  p.co64 = gb_co64(bricks, cout, g.cout_p);
+  g.nct = cdiv(cout, p.co64 ? 64 : 32);
+  p.nunits = (int)(bricks * g.nct);
+  p.per = p.pers ? cdiv(p.nunits, convg_num_cus()) : 1;
+  p.nwg = cdiv(p.nunits, p.per);
+  return p;
+}
+
+// Not the plan's own size but an upper bound over both brick widths and co tiles, so a caller's workspace holds
+// whatever gb_plan chooses: units x 32 channel pairs x 2 doubles (= 128 floats)
+extern "C" long long u3d_convg_brick_stats_ws_floats(int n, int d, int h, int w, int cout) {
+  return (long long)n * cdiv(d, GB_BD) * cdiv(h, GB_BH) * cdiv(w, 8) * cdiv(cout, 32) * 128;
+}
+
+// what a launch passes besides the plan and the geometry (res: the residual, or the GN input x of the fused GroupNorm
+// backward; spart: the forward's statistics partials, or that backward's parts)
+struct GBArgs {
+  const void *x, *wpk;
+  void* y;
+  const void* res;
+  const float *gstat, *gamma, *beta;
+  float* spart;
+  hipStream_t s;
+};
+
+template <int CO, bool FLIP, int BWX, bool GB>
+static void gb_launch(const GBPlan& p, const GBGeom& g, const GBArgs& a) {
+  if (p.pers)
+    hipLaunchKernelGGL((convg_pbrick_kernel<CO, FLIP, BWX, GB>), dim3(p.nwg), dim3(GB_NT), 0, a.s, (const bf16*)a.x,
+                       (const bf16*)a.wpk, (bf16*)a.y, (const bf16*)a.res, a.gstat, a.gamma, a.beta, g, p.per, p.nunits,
+                       a.spart);
+  else
+    hipLaunchKernelGGL((convg_brick_kernel<CO, FLIP>), dim3(p.nwg), dim3(GB_NT), 0, a.s, (const bf16*)a.x,
+                       (const bf16*)a.wpk, (bf16*)a.y, (const bf16*)a.res, a.gstat, a.gamma, a.beta, g);
+}
+
+// the one ladder from the plan to the kernels' template arguments (GB: on the data gradient only)
+template <int CO>
+static void gb_dispatch(bool flip, bool gb, const GBPlan& p, const GBGeom& g, const GBArgs& a) {
+  if (!flip) p.bw8 ? gb_launch<CO, false, 8, false>(p, g, a) : gb_launch<CO, false, 16, false>(p, g, a);
+  else if (gb) p.bw8 ? gb_launch<CO, true, 8, true>(p, g, a) : gb_launch<CO, true, 16, true>(p, g, a);
+  else p.bw8 ? gb_launch<CO, true, 8, false>(p, g, a) : gb_launch<CO, true, 16, false>(p, g, a);
+}
+
 static int convg_impl(int flip, const void* x, int n, int cin, int d, int h, int w, const void* wpk, int cout,
                       const float* gn_stats, const float* gn_gamma, const float* gn_beta, int gn_groups,
                       const void* residual, void* y, float* spart, float* stats_out, u3d_stream_t stream,
@@ -909,101 +989,24 @@ static int convg_impl(int flip, const void* x, int n, int cin, int d, int h, int
   U3D_REQUIRE(cin % 8 == 0 && cout % 8 == 0, "convg_brick: channels must be multiples of 8");
   U3D_REQUIRE(!gn_stats || (gn_gamma && gn_beta && gn_groups > 0 && (gbparts ? cout : cin) % gn_groups == 0),
               "convg_brick: bad GN");
-  GBGeom g{};
-  g.n = n; g.d = d; g.h = h; g.w = w;
-  g.cin = cin; g.cout = cout; g.cin_p = round_up(cin, 32); g.cout_p = round_up(cout, 32);
-  g.nbd = cdiv(d, GB_BD); g.nbh = cdiv(h, GB_BH); g.nbw = cdiv(w, GB_BW);
+  GBGeom g;
+  const GBPlan p = gb_plan(flip, n, cin, d, h, w, cout, gn_stats, residual, gbparts, g);
   g.gn_groups = gn_groups;
-  const int nb = n * g.nbd * g.nbh * g.nbw;
+  U3D_REQUIRE(!spart || (p.pers && !flip && cout % 32 == 0), "convg_brick_stats: needs the persistent forward, cout %% 32 == 0");
+  U3D_REQUIRE(!gbparts || p.pers, "convg_brick_dgrad_gn: needs the persistent data gradient (u3d_convg_brick_gn_nparts)");
+  if (spart && fcnt) {
+    g.fstats = stats_out;
+    g.fcnt = fcnt;
+  }
   hipStream_t s = (hipStream_t)stream;
-  // 64-channel co tiles, unless they give fewer than 128 workgroups and 32-channel tiles give at least 128 (the 24^3 x
-  // 64-channel decoder convs: 72 -> 144 workgroups, fwd 49 -> 25 us, dgrad 40 -> 20 us). Not below that: at 24^3 x 128
-  // channels (144 workgroups with 64-channel tiles) 32-channel tiles measured slower (63.5 -> 78.7 us).
-  // U3D_CONVG_CO32 = 0 / 1 forces the choice (experiments).
-  const int env_co32 = opt(OPT_CONVG_CO32);
-  bool co64 = g.cout_p >= 64;
-  if (co64 && env_co32 == 1) co64 = false;
-  if (co64 && env_co32 < 0 && (long long)nb * cdiv(cout, 64) < 128 && (long long)nb * cdiv(cout, 32) >= 128)
-    co64 = false;
-  g.nct = cdiv(cout, co64 ? 64 : 32);
-  dim3 grid(nb * g.nct);
-  // persistent form (CONVG_PERSIST = 0: the one-shot kernel; u3d_set_option lets a test compare both in-process)
-  const bool pers_on = opt(OPT_CONVG_PERSIST) != 0;
-  // the persistent kernel addresses x and the weight pack with 32-bit buffer offsets
-  const bool small = (long long)n * d * h * w * std::max(cin, cout) * 2 < (1LL << 31) - 64 &&
-                     27LL * g.cout_p * g.cin_p * 2 < (1LL << 31) - 64;
-  // (a data gradient with a residual add — not a trunk routing, kept for the ABI — runs the one-shot kernel: the
-  // persistent data gradient has no residual path, so its epilogue reserves no registers for one)
-  const bool pers = pers_on && small && (!gn_stats || (gbparts ? g.cout_p : g.cin_p) <= GB_MAXC) && !(flip && residual);
-  U3D_REQUIRE(!spart || (pers && !flip && cout % 32 == 0), "convg_brick_stats: needs the persistent forward, cout %% 32 == 0");
-  U3D_REQUIRE(!gbparts || pers, "convg_brick_dgrad_gn: needs the persistent data gradient (u3d_convg_brick_gn_nparts)");
-  if (pers) {
-    const bool bw8 = pbrick_bw8(w);
-    GBGeom gp = g;
-    if (spart && fcnt) {
-      gp.fstats = stats_out;
-      gp.fcnt = fcnt;
-    }
-    if (bw8) {
-      gp.nbw = cdiv(w, 8);
-      const long long nb8 = (long long)n * gp.nbd * gp.nbh * gp.nbw;
-      bool c64 = gp.cout_p >= 64;
-      if (c64 && env_co32 == 1) c64 = false;
-      if (c64 && env_co32 < 0 && nb8 * cdiv(cout, 64) < 128 && nb8 * cdiv(cout, 32) >= 128) c64 = false;
-      co64 = c64;
-      gp.nct = cdiv(cout, co64 ? 64 : 32);
-    }
-    const int nunits = n * gp.nbd * gp.nbh * gp.nbw * gp.nct, per = cdiv(nunits, convg_num_cus()),
-              nwg = cdiv(nunits, per);
-#define U3D_PB(C, F)                                                                                               \
-  do {                                                                                                             \
-    if (F && gbparts) {                                                                                            \
-      if (bw8)                                                                                                     \
-        hipLaunchKernelGGL((convg_pbrick_kernel<C, F, 8, F>), dim3(nwg), dim3(GB_NT), 0, s, (const bf16*)x,       \
-                           (const bf16*)wpk, (bf16*)y, (const bf16*)gbx, gn_stats, gn_gamma, gn_beta, gp, per,     \
-                           nunits, gbparts);                                                                       \
-      else                                                                                                         \
-        hipLaunchKernelGGL((convg_pbrick_kernel<C, F, 16, F>), dim3(nwg), dim3(GB_NT), 0, s, (const bf16*)x,      \
-                           (const bf16*)wpk, (bf16*)y, (const bf16*)gbx, gn_stats, gn_gamma, gn_beta, gp, per,     \
-                           nunits, gbparts);                                                                       \
-    } else if (bw8)                                                                                                \
-      hipLaunchKernelGGL((convg_pbrick_kernel<C, F, 8>), dim3(nwg), dim3(GB_NT), 0, s, (const bf16*)x,          \
-                         (const bf16*)wpk, (bf16*)y, (const bf16*)residual, gn_stats, gn_gamma, gn_beta, gp, per,  \
-                         nunits, spart);                                                                           \
-    else                                                                                                           \
-      hipLaunchKernelGGL((convg_pbrick_kernel<C, F>), dim3(nwg), dim3(GB_NT), 0, s, (const bf16*)x,                \
-                         (const bf16*)wpk, (bf16*)y, (const bf16*)residual, gn_stats, gn_gamma, gn_beta, gp, per,  \
-                         nunits, spart);                                                                           \
-  } while (0)
-    if (co64) {
-      if (flip) U3D_PB(64, true); else U3D_PB(64, false);
-    } else {
-      if (flip) U3D_PB(32, true); else U3D_PB(32, false);
-    }
-#undef U3D_PB
-    int rc = check_launch("convg_pbrick_kernel");
-    if (rc) return rc;
-    if (!spart || fcnt) return rc;  // (fcnt: finalized by the kernel's last-arriving workgroup)
-    hipLaunchKernelGGL(pbrick_gn_finalize_kernel, dim3(n * 16), dim3(256), 0, s, (const double*)spart, co64 ? 64 : 32, gp.nct,
-                       gp.nbd * gp.nbh * gp.nbw, cout, (double)(cout / 16) * d * h * w, stats_out);
-    return check_launch("pbrick_gn_finalize_kernel");
-  }
-  if (co64) {
-    if (flip)
-      hipLaunchKernelGGL((convg_brick_kernel<64, true>), grid, dim3(GB_NT), 0, s, (const bf16*)x, (const bf16*)wpk,
-                         (bf16*)y, (const bf16*)residual, gn_stats, gn_gamma, gn_beta, g);
-    else
-      hipLaunchKernelGGL((convg_brick_kernel<64, false>), grid, dim3(GB_NT), 0, s, (const bf16*)x, (const bf16*)wpk,
-                         (bf16*)y, (const bf16*)residual, gn_stats, gn_gamma, gn_beta, g);
-  } else {
-    if (flip)
-      hipLaunchKernelGGL((convg_brick_kernel<32, true>), grid, dim3(GB_NT), 0, s, (const bf16*)x, (const bf16*)wpk,
-                         (bf16*)y, (const bf16*)residual, gn_stats, gn_gamma, gn_beta, g);
-    else
-      hipLaunchKernelGGL((convg_brick_kernel<32, false>), grid, dim3(GB_NT), 0, s, (const bf16*)x, (const bf16*)wpk,
-                         (bf16*)y, (const bf16*)residual, gn_stats, gn_gamma, gn_beta, g);
-  }
-  return check_launch("convg_brick_kernel");
+  const GBArgs a{x, wpk, y, gbparts ? gbx : residual, gn_stats, gn_gamma, gn_beta, gbparts ? gbparts : spart, s};
+  if (p.co64) gb_dispatch<64>(flip, gbparts, p, g, a);
+  else gb_dispatch<32>(flip, gbparts, p, g, a);
+  int rc = check_launch(p.pers ? "convg_pbrick_kernel" : "convg_brick_kernel");
+  if (rc || !spart || fcnt) return rc;  // (fcnt: finalized by the kernel's last-arriving workgroup)
+  hipLaunchKernelGGL(pbrick_gn_finalize_kernel, dim3(n * 16), dim3(256), 0, s, (const double*)spart, p.co64 ? 64 : 32, g.nct,
+                     g.nbd * g.nbh * g.nbw, cout, (double)(cout / 16) * d * h * w, stats_out);
+  return check_launch("pbrick_gn_finalize_kernel");
 }
 
 extern "C" int u3d_convg_brick(int flip, const void* x, int n, int cin, int d, int h, int w, const void* wpk, int cout,
@@ -1018,10 +1021,8 @@ extern "C" int u3d_convg_brick(int flip, const void* x, int n, int cin, int d, i
 // (nparts = u3d_convg_brick_gn_nparts) = per brick (sum g, sum g*xhat) of g = relu-mask * dA for u3d_gn_bwd_parts.
 // Here cin / cout are the FORWARD conv's channels: dy has cout, x / dA have cin; gn_* is the GroupNorm on x.
 extern "C" int u3d_convg_brick_gn_nparts(int n, int cin, int d, int h, int w, int cout) {
-  const bool small = (long long)n * d * h * w * std::max(cin, cout) * 2 < (1LL << 31) - 64 &&
-                     27LL * round_up(cin, 32) * round_up(cout, 32) * 2 < (1LL << 31) - 64;
-  if (opt(OPT_CONVG_PERSIST) == 0 || !small || round_up(cin, 32) > GB_MAXC || n < 1 || n > GB_MAXN) return 0;
-  return cdiv(d, GB_BD) * cdiv(h, GB_BH) * cdiv(w, pbrick_bw8(w) ? 8 : GB_BW);
+  GBGeom g;
+  return gb_plan(true, n, cout, d, h, w, cin, true, false, true, g).pers ? g.nbd * g.nbh * g.nbw : 0;
 }
 
 extern "C" int u3d_convg_brick_dgrad_gn(const void* dy, int n, int cout, int d, int h, int w, const void* wpk_dgrad,
@@ -1032,11 +1033,6 @@ extern "C" int u3d_convg_brick_dgrad_gn(const void* dy, int n, int cout, int d, 
               "convg_brick_dgrad_gn: parts layout (u3d_convg_brick_gn_nparts) mismatch");
   return convg_impl(1, dy, n, cout, d, h, w, wpk_dgrad, cin, gn_stats, gn_gamma, gn_beta, gn_groups, nullptr, dx,
                     nullptr, nullptr, stream, x, parts);
-}
-
-extern "C" long long u3d_convg_brick_stats_ws_floats(int n, int d, int h, int w, int cout) {
-  // upper bound over both brick widths and co tiles: units x 32 channel pairs x 2 doubles (= 128 floats)
-  return (long long)n * cdiv(d, GB_BD) * cdiv(h, GB_BH) * cdiv(w, 8) * cdiv(cout, 32) * 128;
 }
 
 extern "C" int u3d_convg_brick_stats(const void* x, int n, int cin, int d, int h, int w, const void* wpk, int cout,

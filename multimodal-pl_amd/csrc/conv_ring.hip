@@ -38,9 +38,6 @@ constexpr int RG_NWR = 27 * 32;                      // weight rows (t, co)
 #ifndef U3D_ABL_RING
 #define U3D_ABL_RING 0
 #endif
-#ifndef RG_HOIST
-#define RG_HOIST 1
-#endif
 // -DU3D_STAMPS phases (diag.h): 0 the steps' MFMAs + the staging side work between them, 1 the steps' heads (claims,
 // GN table, walk), 2 the barriers
 U3D_STAMP_BUFFER(rg_stamps, 2048, u3d_diag_ring_stamps)
@@ -132,7 +129,7 @@ __global__ __launch_bounds__(RG_NT, 1) void conv32_ring_kernel(const bf16* __res
   // per channel (sum g, sum g*xhat) of g = relu-mask * dA go to spart[workgroup][32][2] (u3d_gn_bwd_parts finishes)
   constexpr bool PRO = GN && !FLIP, GB = GN && FLIP, LDR = RES || GB;
   static_assert(!(GB && (Q || RES)), "the fused GroupNorm backward runs on the static data-gradient ring only");
-  static_assert(!XN || (PRO && !Q && RG_HOIST), "the normalised side output belongs to the static GN forward");
+  static_assert(!XN || (PRO && !Q), "the normalised side output belongs to the static GN forward");
   __shared__ __attribute__((aligned(16))) char smem[4 * RG_SS + 4 * RG_NWR * 16 + 1024 + 512 + (GB ? 576 : 0)];
   char* const ring = smem;
   char* const wts = smem + 4 * RG_SS;
@@ -246,10 +243,9 @@ __global__ __launch_bounds__(RG_NT, 1) void conv32_ring_kernel(const bf16* __res
   int gn_n = -1;
   // branch-free staging: out-of-volume rows load a valid dummy address and are zeroed when written
   // staged piece i of plane p (16 B of one halo row) into v[i]; bit i of m = the row is inside the volume
-  // (round 4, RG_HOIST) a lane's halo row of piece i is the same in every plane: its byte offset is a per-lane constant
+  // (round 4) a lane's halo row of piece i is the same in every plane: its byte offset is a per-lane constant
   // plus a wave-uniform plane base, and its in-volume test changes only with the column — per piece and plane one add
   // and one select instead of the integer address math (r04 stamps / ISA: issue slots the MFMA chain needs)
-#if RG_HOIST
   int plo[RG_LD];
 #pragma unroll
   for (int i = 0; i < RG_LD; ++i) {
@@ -266,10 +262,8 @@ __global__ __launch_bounds__(RG_NT, 1) void conv32_ring_kernel(const bf16* __res
       pint |= (row < RG_NR && hh >= 1 && hh <= RG_BH && hw >= 1 && hw <= RG_BW ? 1u : 0u) << i;
     }
   }
-#endif
   const auto nrs = __builtin_amdgcn_make_buffer_rsrc((void*)xno, 0, XN ? (int)g.xbytes : 0, 0x00020000);
   auto load_piece = [&](const RGPlane& p, int i, u32x4 (&v)[RG_LD], unsigned& m) {
-#if RG_HOIST
     if (i == 0 && p.valid && (p.h0 != col_h0 || p.w0 != col_w0)) {  // uniform: once per run of the walk
       col_h0 = p.h0;
       col_w0 = p.w0;
@@ -285,14 +279,6 @@ __global__ __launch_bounds__(RG_NT, 1) void conv32_ring_kernel(const bf16* __res
     const int base = (((p.n * g.d + p.zin) * g.h + p.h0 - 1) * g.w + p.w0 - 1) * 64;
     const bool ok = p.valid && (unsigned)p.zin < (unsigned)g.d && ((pin >> i) & 1u);
     const unsigned off = ok ? (unsigned)(base + plo[i]) : 0xFFFFFFF0u;
-#else
-    const int row = srow + i * (RG_NT / 4);
-    const int hw = row % RG_HW, hh = row / RG_HW;
-    const int zh = p.h0 - 1 + hh, zw = p.w0 - 1 + hw;
-    const bool ok = p.valid && row < RG_NR && (unsigned)p.zin < (unsigned)g.d && (unsigned)zh < (unsigned)g.h &&
-                    (unsigned)zw < (unsigned)g.w;
-    const unsigned off = ok ? (unsigned)((((p.n * g.d + p.zin) * g.h + zh) * g.w + zw) * 64 + ch * 16) : 0xFFFFFFF0u;
-#endif
     v[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(xrs, off, 0, 0));
     m = (i == 0 ? 0u : m) | ((ok ? 1u : 0u) << i);
   };
@@ -315,12 +301,10 @@ __global__ __launch_bounds__(RG_NT, 1) void conv32_ring_kernel(const bf16* __res
 #endif
     char* dst = row < RG_NR ? ring + slot * RG_SS + ch * RG_PS + row * 16 : junk + (tid & 63) * 16;
     *reinterpret_cast<u32x4*>(dst) = val;
-#if RG_HOIST
     if constexpr (XN) {  // the tile's own in-volume rows: an out-of-range offset drops the store (no branch)
       const unsigned off = ((m & pint) >> i) & 1u ? (unsigned)(xbase + plo[i]) : 0xFFFFFFF0u;
       __builtin_amdgcn_raw_buffer_store_b128(val, nrs, off, 0, 0);
     }
-#endif
   };
 
   // A computed output plane waiting for its epilogue: the epilogue (bf16 pack, permlane swap, residual add,
@@ -841,72 +825,12 @@ static int ring_kr(int dflt) {  // RING_KR = 0: no weight steps in registers (ex
 }
 
 static int ring_wgs() { return std::max(1, opt(OPT_RING_WGS)); }  // persistent grid target: one workgroup per CU
-static int conv32_ring_impl(int flip, const void* x, int n, int d, int h, int w, const void* wpk,
-                            const float* gn_stats, const float* gn_gamma, const float* gn_beta, int gn_groups,
-                            const void* residual, void* y, float* stats_out, float* stats_ws, u3d_stream_t stream,
-                            float* fstats = nullptr, unsigned* fcnt = nullptr, void* xn = nullptr) {
-  U3D_REQUIRE(x && wpk && y && n >= 1 && d >= 1 && h >= 1 && w >= 1, "conv32_ring: bad args");
-  U3D_REQUIRE(!gn_stats || (gn_gamma && gn_beta && gn_groups > 0 && 32 % gn_groups == 0), "conv32_ring: bad GN");
-  U3D_REQUIRE(!stats_out || (gn_stats && stats_ws), "conv32_ring: output statistics need the GN prologue + ws");
-  U3D_REQUIRE(!xn || (gn_stats && !flip && xn != x), "conv32_ring: the normalised side output needs the GN prologue");
-  RGGeom g{};
-  g.n = n; g.d = d; g.h = h; g.w = w;
-  g.nbh = cdiv(h, RG_BH); g.nbw = cdiv(w, RG_BW);
-  g.pps = (long long)g.nbh * g.nbw * d;
-  g.planes = (long long)n * g.pps;
-  g.xbytes = (long long)n * d * h * w * 64;
-  U3D_REQUIRE(g.xbytes < (1LL << 31), "conv32_ring: tensor of %lld bytes beyond the 2 GiB buffer-offset range",
-              g.xbytes);
-  // ~256 persistent workgroups, split evenly per sample (no workgroup straddles two samples)
-  const long long wps0 = std::max<long long>(1, std::min<long long>(g.pps, ring_wgs() / n));
-  g.per = (int)((g.pps + wps0 - 1) / wps0);
-  g.wps = (int)((g.pps + g.per - 1) / g.per);
-  const long long grid = (long long)n * g.wps;
-  g.gn_groups = gn_groups;
-  if (stats_out && fcnt && fstats) {
-    g.fstats = fstats;
-    g.fcnt = fcnt;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  float* sp = stats_out ? stats_ws : nullptr;
-#define RG_LAUNCH(F, G, R, K)                                                                                  \
-  hipLaunchKernelGGL((conv32_ring_kernel<F, G, R, K>), dim3((unsigned)grid), dim3(RG_NT), 0, s, (const bf16*)x, \
-                     (const bf16*)wpk, (bf16*)y, (const bf16*)residual, gn_stats, gn_gamma, gn_beta, sp, g)
-#define RG_KR(F, G, R, K)                  \
-  do {                                     \
-    if (kr) RG_LAUNCH(F, G, R, K);         \
-    else RG_LAUNCH(F, G, R, 0);            \
-  } while (0)
-  U3D_REQUIRE(!(flip && (gn_stats || residual)), "conv32_ring: the data gradient takes no prologue / residual");
-  // register budget (2 waves per SIMD): GN + residual holds 12 weight steps, GN 16, the others 27
-  const bool kr = ring_kr(1) != 0;
-  if (xn) {  // (two weight steps fewer: the side store's offsets)
-#define RG_XN(R, K)                                                                                                 \
-  hipLaunchKernelGGL((conv32_ring_kernel<false, true, R, K, false, true>), dim3((unsigned)grid), dim3(RG_NT), 0, s, \
-                     (const bf16*)x, (const bf16*)wpk, (bf16*)y, (const bf16*)residual, gn_stats, gn_gamma, gn_beta, \
-                     sp, g, nullptr, (bf16*)xn)
-    if (residual) RG_XN(true, U3D_RING_XN_KR_RES);
-    else RG_XN(false, U3D_RING_XN_KR);
-#undef RG_XN
-    return check_launch("conv32_ring_kernel (normalised side output)");
-  }
-  if (flip) RG_KR(true, false, false, 27);
-  else if (gn_stats && residual) RG_KR(false, true, true, 12);  // + the statistics accumulators: 12 steps
-  else if (gn_stats) RG_KR(false, true, false, 16);  // (12 measured equal: 124.6 vs 124.8 us)
-  else if (residual) RG_KR(false, false, true, 20);
-  else RG_KR(false, false, false, 27);
-#undef RG_KR
-#undef RG_LAUNCH
-  return check_launch("conv32_ring_kernel");
-}
 
-// ------------------------------------------------------------------------------------------- work-stealing mode
-static int ring_sc_env() { return opt(OPT_RING_SC); }  // output planes per sub-chunk (0 = default)
-
-// the static split of conv32_ring_impl (~256 workgroups, ranges of `per` planes never straddling samples), each
-// range cut into sub-chunks of about a ninth of it (>= 3 planes); a third when the launch accumulates GroupNorm
-// statistics (each sub-chunk boundary costs a per-wave reduction inside the MFMA chain)
-static void ring_q_geom(int n, int d, int h, int w, RGGeom& g, bool stats = false) {
+// The launch plan of every ring kernel and of every size query: ~256 persistent workgroups, split evenly per sample
+// into ranges of `per` output planes (no workgroup straddles two samples), wps of them per sample. Launchers, workspace
+// queries and finalizes all take the split from here, so a partials buffer is never read with another wps than it was
+// written with. Callers check xbytes against the 2 GiB buffer-offset range (under their own name).
+static void rg_geom(int n, int d, int h, int w, RGGeom& g) {
   g = RGGeom{};
   g.n = n; g.d = d; g.h = h; g.w = w;
   g.nbh = cdiv(h, RG_BH); g.nbw = cdiv(w, RG_BW);
@@ -916,6 +840,15 @@ static void ring_q_geom(int n, int d, int h, int w, RGGeom& g, bool stats = fals
   const long long wps0 = std::max<long long>(1, std::min<long long>(g.pps, ring_wgs() / n));
   g.per = (int)((g.pps + wps0 - 1) / wps0);
   g.wps = (int)((g.pps + g.per - 1) / g.per);
+}
+
+static int ring_sc_env() { return opt(OPT_RING_SC); }  // output planes per sub-chunk (0 = default)
+
+// work-stealing mode: the static split of rg_geom, each range cut into sub-chunks of about a ninth of it (>= 3
+// planes); a third when the launch accumulates GroupNorm statistics (each sub-chunk boundary costs a per-wave
+// reduction inside the MFMA chain)
+static void ring_q_geom(int n, int d, int h, int w, RGGeom& g, bool stats = false) {
+  rg_geom(n, d, h, w, g);
   const int env = ring_sc_env();
   // >= 3 planes: a claim's verdict (two steps after its first plane is staged) lands before the next boundary
   const int parts = stats ? 3 : 9;
@@ -923,7 +856,108 @@ static void ring_q_geom(int n, int d, int h, int w, RGGeom& g, bool stats = fals
   g.rmax = (g.per + g.sc - 1) / g.sc;
 }
 
+// KR, the weight steps (tap, co block) a variant keeps in registers — the register budget at 2 waves per SIMD:
+//   static          GN + residual holds 12 (+ the statistics accumulators), GN 16 (12 measured equal: 124.6 vs
+//                   124.8 us), residual 20, the others 27
+//   work stealing   the claim state costs the static variants' weight steps a few registers
+//   XN              two weight steps fewer than the static GN forms: the side store's offsets
+//   GB              (data gradient + GroupNorm-backward partials) beside the fused GroupNorm-backward state
+constexpr int rg_kr(bool flip, bool gn, bool res, bool q, bool xn) {
+  if (xn) return res ? U3D_RING_XN_KR_RES : U3D_RING_XN_KR;
+  if (flip && gn) return U3D_RING_GB_KR;
+  if (q) return flip ? 16 : gn ? (res ? 4 : 8) : res ? 14 : 16;
+  return flip ? 27 : gn ? (res ? 12 : 16) : res ? 20 : 27;
+}
 
+// what a ring launch passes besides the geometry (res: the residual; x of the forward for the fused GN backward)
+struct RGArgs {
+  const void *x, *wpk;
+  void* y;
+  const void* res;
+  const float *gstat, *gamma, *beta;
+  float* spart;
+  hipStream_t s;
+  int* queue = nullptr;
+  void* xno = nullptr;
+};
+
+template <bool FLIP, bool GN, bool RES, int KR, bool Q = false, bool XN = false>
+static void rg_launch(const RGGeom& g, const RGArgs& a) {
+  hipLaunchKernelGGL((conv32_ring_kernel<FLIP, GN, RES, KR, Q, XN>), dim3((unsigned)(g.n * g.wps)), dim3(RG_NT), 0, a.s,
+                     (const bf16*)a.x, (const bf16*)a.wpk, (bf16*)a.y, (const bf16*)a.res, a.gstat, a.gamma, a.beta,
+                     a.spart, g, a.queue, (bf16*)a.xno);
+}
+
+// the variant at its KR of the table; the static forms also exist with KR = 0 (RING_KR = 0)
+template <bool FLIP, bool GN, bool RES, bool Q = false, bool XN = false>
+static void rg_launch_kr(const RGGeom& g, const RGArgs& a) {
+  if constexpr (!Q && !XN)
+    if (ring_kr(1) == 0) return rg_launch<FLIP, GN, RES, 0>(g, a);
+  rg_launch<FLIP, GN, RES, rg_kr(FLIP, GN, RES, Q, XN), Q, XN>(g, a);
+}
+
+template <bool Q>
+static void rg_launch_conv(bool flip, bool gn, bool res, const RGGeom& g, const RGArgs& a) {
+  if (flip) rg_launch_kr<true, false, false, Q>(g, a);
+  else if (gn && res) rg_launch_kr<false, true, true, Q>(g, a);
+  else if (gn) rg_launch_kr<false, true, false, Q>(g, a);
+  else if (res) rg_launch_kr<false, false, true, Q>(g, a);
+  else rg_launch_kr<false, false, false, Q>(g, a);
+}
+
+static int conv32_ring_impl(int flip, const void* x, int n, int d, int h, int w, const void* wpk,
+                            const float* gn_stats, const float* gn_gamma, const float* gn_beta, int gn_groups,
+                            const void* residual, void* y, float* stats_out, float* stats_ws, u3d_stream_t stream,
+                            float* fstats = nullptr, unsigned* fcnt = nullptr, void* xn = nullptr) {
+  U3D_REQUIRE(x && wpk && y && n >= 1 && d >= 1 && h >= 1 && w >= 1, "conv32_ring: bad args");
+  U3D_REQUIRE(!gn_stats || (gn_gamma && gn_beta && gn_groups > 0 && 32 % gn_groups == 0), "conv32_ring: bad GN");
+  U3D_REQUIRE(!stats_out || (gn_stats && stats_ws), "conv32_ring: output statistics need the GN prologue + ws");
+  U3D_REQUIRE(!xn || (gn_stats && !flip && xn != x), "conv32_ring: the normalised side output needs the GN prologue");
+  RGGeom g;
+  rg_geom(n, d, h, w, g);
+  U3D_REQUIRE(g.xbytes < (1LL << 31), "conv32_ring: tensor of %lld bytes beyond the 2 GiB buffer-offset range",
+              g.xbytes);
+  g.gn_groups = gn_groups;
+  if (stats_out && fcnt && fstats) {
+    g.fstats = fstats;
+    g.fcnt = fcnt;
+  }
+  U3D_REQUIRE(!(flip && (gn_stats || residual)), "conv32_ring: the data gradient takes no prologue / residual");
+  const RGArgs a{x, wpk, y, residual, gn_stats, gn_gamma, gn_beta, stats_out ? stats_ws : nullptr,
+                 (hipStream_t)stream, nullptr, xn};
+  if (xn) {
+    if (residual) rg_launch_kr<false, true, true, false, true>(g, a);
+    else rg_launch_kr<false, true, false, false, true>(g, a);
+    return check_launch("conv32_ring_kernel (normalised side output)");
+  }
+  rg_launch_conv<false>(flip, gn_stats, residual, g, a);
+  return check_launch("conv32_ring_kernel");
+}
+
+static int ring_dgrad_gn_impl(const void* dy, int n, int d, int h, int w, const void* wpk_dgrad, const void* x,
+                              const float* gn_stats, const float* gn_gamma, const float* gn_beta, int gn_groups,
+                              void* da, float* parts, float* coef, float* dgamma, float* dbeta, unsigned* cnt,
+                              u3d_stream_t stream) {
+  U3D_REQUIRE(dy && wpk_dgrad && x && da && parts && n >= 1 && d >= 1 && h >= 1 && w >= 1,
+              "conv32_ring_dgrad_gn: bad args");
+  U3D_REQUIRE(gn_stats && gn_gamma && gn_beta && gn_groups > 0 && 32 % gn_groups == 0, "conv32_ring_dgrad_gn: bad GN");
+  RGGeom g;
+  rg_geom(n, d, h, w, g);
+  U3D_REQUIRE(g.xbytes < (1LL << 31), "conv32_ring_dgrad_gn: tensor of %lld bytes beyond the 2 GiB buffer-offset range",
+              g.xbytes);
+  g.gn_groups = gn_groups;
+  if (cnt) {
+    g.fcnt = cnt;
+    g.coef = coef;
+    g.dgamma = dgamma;
+    g.dbeta = dbeta;
+  }
+  const RGArgs a{dy, wpk_dgrad, da, x, gn_stats, gn_gamma, gn_beta, parts, (hipStream_t)stream};
+  rg_launch_kr<true, true, false>(g, a);
+  return check_launch("conv32_ring_dgrad_gn");
+}
+
+// ------------------------------------------------------------------------------------------- work-stealing mode
 extern "C" int u3d_conv32_ring_q_stats_ws_floats(int n, int d, int h, int w) {
   RGGeom g;
   ring_q_geom(n, d, h, w, g, true);
@@ -948,18 +982,8 @@ extern "C" int u3d_conv32_ring_q(int flip, const void* x, int n, int d, int h, i
   U3D_REQUIRE(g.xbytes < (1LL << 31), "conv32_ring_q: tensor of %lld bytes beyond the 2 GiB buffer-offset range",
               g.xbytes);
   g.gn_groups = gn_groups;
-  const unsigned grid = (unsigned)(n * g.wps);
-  hipStream_t s = (hipStream_t)stream;
-#define RQ_LAUNCH(F, G, R, K)                                                                                     \
-  hipLaunchKernelGGL((conv32_ring_kernel<F, G, R, K, true>), dim3(grid), dim3(RG_NT), 0, s, (const bf16*)x, \
-                     (const bf16*)wpk, (bf16*)y, (const bf16*)residual, gn_stats, gn_gamma, gn_beta, stats_ws, g, queue)
-  // register budget: the claim state costs the weight steps of the static variants a few registers
-  if (flip) RQ_LAUNCH(true, false, false, 16);
-  else if (gn_stats && residual) RQ_LAUNCH(false, true, true, 4);
-  else if (gn_stats) RQ_LAUNCH(false, true, false, 8);
-  else if (residual) RQ_LAUNCH(false, false, true, 14);
-  else RQ_LAUNCH(false, false, false, 16);
-#undef RQ_LAUNCH
+  rg_launch_conv<true>(flip, gn_stats, residual, g,
+                       RGArgs{x, wpk, y, residual, gn_stats, gn_gamma, gn_beta, stats_ws, (hipStream_t)stream, queue});
   return check_launch("conv32_ring_kernel (work stealing)");
 }
 
@@ -1023,16 +1047,10 @@ extern "C" int u3d_conv32_ring(int flip, const void* x, int n, int d, int h, int
 // partial pass, groupnorm.hip). u3d_gn_bwd_parts then writes dx. Static schedule only (deterministic partials).
 extern "C" int u3d_conv32_ring_wps(int n, int d, int h, int w) {
   if (n < 1 || d < 1 || h < 1 || w < 1) return -1;
-  const long long pps = (long long)cdiv(h, RG_BH) * cdiv(w, RG_BW) * d;
-  const long long wps0 = std::max<long long>(1, std::min<long long>(pps, ring_wgs() / n));
-  const long long per = (pps + wps0 - 1) / wps0;
-  return (int)((pps + per - 1) / per);
+  RGGeom g;
+  rg_geom(n, d, h, w, g);
+  return g.wps;
 }
-
-static int ring_dgrad_gn_impl(const void* dy, int n, int d, int h, int w, const void* wpk_dgrad, const void* x,
-                              const float* gn_stats, const float* gn_gamma, const float* gn_beta, int gn_groups,
-                              void* da, float* parts, float* coef, float* dgamma, float* dbeta, unsigned* cnt,
-                              u3d_stream_t stream);
 
 extern "C" int u3d_conv32_ring_dgrad_gn(const void* dy, int n, int d, int h, int w, const void* wpk_dgrad,
                                         const void* x, const float* gn_stats, const float* gn_gamma,
@@ -1052,43 +1070,6 @@ extern "C" int u3d_conv32_ring_dgrad_gn_fused(const void* dy, int n, int d, int 
   U3D_REQUIRE(coef && cnt && n * 32 * 2 * 8 <= 4 * RG_SS, "conv32_ring_dgrad_gn_fused: bad args");
   return ring_dgrad_gn_impl(dy, n, d, h, w, wpk_dgrad, x, gn_stats, gn_gamma, gn_beta, gn_groups, da, parts, coef,
                             dgamma, dbeta, cnt, stream);
-}
-
-static int ring_dgrad_gn_impl(const void* dy, int n, int d, int h, int w, const void* wpk_dgrad, const void* x,
-                              const float* gn_stats, const float* gn_gamma, const float* gn_beta, int gn_groups,
-                              void* da, float* parts, float* coef, float* dgamma, float* dbeta, unsigned* cnt,
-                              u3d_stream_t stream) {
-  U3D_REQUIRE(dy && wpk_dgrad && x && da && parts && n >= 1 && d >= 1 && h >= 1 && w >= 1,
-              "conv32_ring_dgrad_gn: bad args");
-  U3D_REQUIRE(gn_stats && gn_gamma && gn_beta && gn_groups > 0 && 32 % gn_groups == 0, "conv32_ring_dgrad_gn: bad GN");
-  RGGeom g{};
-  g.n = n; g.d = d; g.h = h; g.w = w;
-  g.nbh = cdiv(h, RG_BH); g.nbw = cdiv(w, RG_BW);
-  g.pps = (long long)g.nbh * g.nbw * d;
-  g.planes = (long long)n * g.pps;
-  g.xbytes = (long long)n * d * h * w * 64;
-  U3D_REQUIRE(g.xbytes < (1LL << 31), "conv32_ring_dgrad_gn: tensor of %lld bytes beyond the 2 GiB buffer-offset range",
-              g.xbytes);
-  const long long wps0 = std::max<long long>(1, std::min<long long>(g.pps, ring_wgs() / n));
-  g.per = (int)((g.pps + wps0 - 1) / wps0);
-  g.wps = (int)((g.pps + g.per - 1) / g.per);
-  g.gn_groups = gn_groups;
-  if (cnt) {
-    g.fcnt = cnt;
-    g.coef = coef;
-    g.dgamma = dgamma;
-    g.dbeta = dbeta;
-  }
-  const long long grid = (long long)n * g.wps;
-  const bool kr = ring_kr(1) != 0;
-#define RG_GB(K)                                                                                               \
-  hipLaunchKernelGGL((conv32_ring_kernel<true, true, false, K>), dim3((unsigned)grid), dim3(RG_NT), 0,         \
-                     (hipStream_t)stream, (const bf16*)dy, (const bf16*)wpk_dgrad, (bf16*)da, (const bf16*)x,  \
-                     gn_stats, gn_gamma, gn_beta, parts, g)
-  if (kr) RG_GB(U3D_RING_GB_KR);
-  else RG_GB(0);
-#undef RG_GB
-  return check_launch("conv32_ring_dgrad_gn");
 }
 
 extern "C" int u3d_conv32_ring_stats_ws_floats(int n) { return 64 * std::max(256, n); }
@@ -1115,11 +1096,9 @@ extern "C" int u3d_conv32_ring_stats_xn(const void* x, int n, int d, int h, int 
 extern "C" int u3d_conv32_ring_stats_finalize(const float* stats_ws, int n, int d, int h, int w, float* stats_out,
                                               u3d_stream_t stream) {
   U3D_REQUIRE(stats_ws && stats_out && n >= 1 && d >= 1 && h >= 1 && w >= 1, "conv32_ring_stats_finalize: bad args");
-  const long long pps = (long long)cdiv(h, RG_BH) * cdiv(w, RG_BW) * d;  // same split as conv32_ring_impl
-  const long long wps0 = std::max<long long>(1, std::min<long long>(pps, ring_wgs() / n));
-  const long long per = (pps + wps0 - 1) / wps0;
-  const int wps = (int)((pps + per - 1) / per);
-  hipLaunchKernelGGL(ring_gn_finalize_kernel, dim3(n * 16), dim3(256), 0, (hipStream_t)stream, stats_ws, n, wps,
+  RGGeom g;
+  rg_geom(n, d, h, w, g);
+  hipLaunchKernelGGL(ring_gn_finalize_kernel, dim3(n * 16), dim3(256), 0, (hipStream_t)stream, stats_ws, n, g.wps,
                      2.0 * d * h * w, stats_out);
   return check_launch("ring_gn_finalize_kernel");
 }

@@ -136,7 +136,8 @@ static int conv_small_impl(int flip, const void* x, int n, int cin, int d, int h
               "conv_small2: statistics form limits");
   const long long nwg = tiles * g.nks;
   U3D_REQUIRE(nwg < (1LL << 31), "conv_small: grid too large");
-  U3D_REQUIRE((long long)n * d * h * w * std::max(cin, cout) * 2 < (1LL << 31) - 64 && 27LL * g.cout_p * g.cin_p * 2 < (1LL << 31) - 64,
+  U3D_REQUIRE(fits_buffer_offsets((long long)n * d * h * w * std::max(cin, cout) * 2) &&
+                  fits_buffer_offsets(27LL * g.cout_p * g.cin_p * 2),
               "conv_small: operands beyond the 2 GiB buffer-offset range");
   hipStream_t s = (hipStream_t)stream;
   if (flip)

@@ -238,8 +238,8 @@ extern "C" int u3d_conv_dgrad_s2(const void* dy, int n, int cout, const void* wp
   g.nct = g.cx_p / 32;
   const long long nwg = (long long)n * g.nbd * g.nbh * g.nbw * g.nct;
   U3D_REQUIRE(nwg < (1LL << 31), "conv_dgrad_s2: grid too large");
-  U3D_REQUIRE((long long)n * g.qd * g.qh * g.qw * g.cy * 2 < (1LL << 31) - 64 &&
-              27LL * g.cx_p * g.cy_p * 2 < (1LL << 31) - 64,
+  U3D_REQUIRE(fits_buffer_offsets((long long)n * g.qd * g.qh * g.qw * g.cy * 2) &&
+                  fits_buffer_offsets(27LL * g.cx_p * g.cy_p * 2),
               "conv_dgrad_s2: dy / weights beyond the 2 GiB buffer-offset range");
   hipLaunchKernelGGL(dgrad_s2_kernel, dim3((unsigned)nwg), dim3(S2_NT), 0, (hipStream_t)stream, (const bf16*)dy,
                      (const bf16*)wpk_dgrad, (bf16*)dx, g);

@@ -96,9 +96,10 @@ static bool pair_plan(int n, int cout, int d, int h, int w, int cin, int ring, f
   const long long tiles = sc_plan(n, cout, d, h, w, cin, 0, ws, ws_bytes, p.ga);
   if (p.ga.nks < 2 || p.ga.nks > 8 || (long long)n * cin * 2 > 8192) return false;
   p.nA = tiles * p.ga.nks;
-  const long long vox = (long long)n * d * h * w, lim = (1LL << 31) - 64;
+  const long long vox = (long long)n * d * h * w;
   const int cin_p = round_up(cin, 32), cout_p = round_up(cout, 32);
-  if (vox * std::max(cin, cout) * 2 >= lim || 27LL * cout_p * cin_p * 2 >= lim || p.ga.nks * vox * cin * 4 >= lim)
+  if (!fits_buffer_offsets(vox * std::max(cin, cout) * 2) || !fits_buffer_offsets(27LL * cout_p * cin_p * 2) ||
+      !fits_buffer_offsets(p.ga.nks * vox * cin * 4))
     return false;  // 32-bit buffer offsets: operands, weight pack, split-K slabs
   // ---- the weight gradient: the kernel u3d_conv_wgrad_ring / u3d_conv_wgrad_brick would launch
   p.ring = ring != 0;

@@ -239,8 +239,8 @@ extern "C" int u3d_conv_wgrad_brick(const void* dy, const void* x, int n, int ci
   const int nco = wb_nco(stride, cout);
   dim3 grid(g.cin_p / 32, g.cout_p / 32 / nco, ns_eff);
   // buffer loads where both operands fit the 32-bit offset range (the > 2 GiB whole-volume case keeps 64-bit loads)
-  const bool buf = (long long)n * g.od * g.oh * g.ow * cout * 2 < (1LL << 31) - 64 &&
-                   (long long)n * d * h * w * cin * 2 < (1LL << 31) - 64;
+  const bool buf = fits_buffer_offsets((long long)n * g.od * g.oh * g.ow * cout * 2) &&
+                   fits_buffer_offsets((long long)n * d * h * w * cin * 2);
 #define U3D_WB(BD_, BH_, BW_, S_, NCO_)                                                                            \
   do {                                                                                                             \
     if (buf)                                                                                                       \
@@ -292,7 +292,7 @@ extern "C" int u3d_conv_wgrad1(const void* dy, const void* x, int n, int cin, in
                            (size_t)(nsplit - ns_eff) * g.cout_p * g.cin_p * 4, s));
   dim3 grid(g.cin_p / 32, g.cout_p / 32, ns_eff);
   // buffer loads and 32-bit indices where both operands fit the 32-bit offset range
-  const bool buf = g.nvox * cout * 2 < (1LL << 31) - 64 && (long long)n * d * h * w * cin * 2 < (1LL << 31) - 64;
+  const bool buf = fits_buffer_offsets(g.nvox * cout * 2) && fits_buffer_offsets((long long)n * d * h * w * cin * 2);
 #define U3D_W1(S_)                                                                                                \
   do {                                                                                                            \
     if (buf)                                                                                                      \
