@@ -567,6 +567,35 @@ int u3d_eam_attn_bwd(int dtype, const void* x, int n, long long v, int c, const 
 int u3d_eam_param_bwd(const float* dm, int nt, int c, const float* zhat, const float* g3, const float* b3,
                       const float* wq, const float* wk, const float* q, float inv_heads, float* dq_ws, float* dz_ws,
                       float* dwq, float* dkv, float* dg3, float* db3, int accumulate, u3d_stream_t stream);
+/* EAM class message (unet3D.py:186-212), the half of EAM that unet3D_with_eam / _eam_baseline keep: attention pooling
+ * of one level x [1][v][c] (dtype NDHWC, c in {32, 64, 128}) against nt <= 16 tokens x heads = 4 (eam_pool.hip).
+ * hd = c / heads, scale = hd^-0.5, head i owns channels i hd .. (i + 1) hd - 1, Wk = kv.weight[:c], Wv = kv.weight[c:],
+ * xhat_n = LayerNorm-normalised x_n (eps 1e-5, biased variance), u_n = xhat_n g2 + b2, row r = i nt + t.
+ *   token side (caller, before):  z = LN3(tok) g3 + b3, q = z Wq^T, a[r] = q[t, head i] Wk[head i, :]     a [4 nt][c]
+ *   voxel side (u3d_eam_pool_fwd): S[r][n] = a[r] . u_n
+ *                                  att[t][n] = 1/4 sum_i S[i nt + t][n]       (optional; u3d_eam_attn_fwd's map)
+ *                                  P[r][.] = softmax_n(scale S[r][.])
+ *                                  yhat[r] = sum_n P[r][n] xhat_n                                       yhat [4 nt][c]
+ *                                  stat[r] = max_n scale S[r][n], stat[4 nt + r] = sum_n exp(scale S[r][n] - max)
+ *   token side (caller, after):   Y = yhat g2 + b2 (sum_n P = 1), O[t, head i] = Wv[head i, :] . Y[i nt + t],
+ *                                  cm = proj(LN2(O)) + O
+ * Backward of the voxel side, one pass over x recomputing xhat, S and P from stat; given dyhat [4 nt][c] with
+ * d[r] = sum_c dyhat[r][c] yhat[r][c] (both or neither) and gatt [nt][v] (optional):
+ *   dP = dyhat[r] . xhat_n,  dS = scale P (dP - d[r]) + gatt[t][n] / 4,  dl_n = sum_r dS[r][n] a[r]
+ *   dxhat_n = sum_r P[r][n] dyhat[r] + g2 dl_n,  dx_n = LayerNorm backward of dxhat_n  (+= when accumulate)
+ *   da[r] = sum_n dS[r][n] u_n,  dg2 = sum_n dl_n xhat_n,  db2 = sum_n dl_n            (dg2 / db2 += when acc_params)
+ * Each workgroup walks its 64-voxel tiles with a running maximum per row (online softmax) and leaves per-row
+ * partials in `part` (u3d_eam_pool_part_floats floats, constant in v past u3d_eam_pool_blocks' cap); a combine
+ * kernel merges them in block order. No float atomics: bitwise reproducible. n != 1 is U3D_EUNSUPPORTED. */
+int u3d_eam_pool_blocks(long long v);
+long long u3d_eam_pool_part_floats(long long v, int c, int nt);
+int u3d_eam_pool_fwd(int dtype, const void* x, int n, long long v, int c, const float* g2, const float* b2,
+                     const float* a, int nt, int heads, float scale, float* att, float* yhat, float* stat, float* part,
+                     u3d_stream_t stream);
+int u3d_eam_pool_bwd(int dtype, const void* x, int n, long long v, int c, const float* g2, const float* b2,
+                     const float* a, int nt, int heads, float scale, const float* stat, const float* dyhat,
+                     const float* d, const float* gatt, void* dx, int accumulate, float* part, float* da, float* dg2,
+                     float* db2, int acc_params, u3d_stream_t stream);
 /* nn.Upsample(scale_factor=s, mode='trilinear'), align_corners=False (unet3D.py:963-965, deep_up maps): NCDHW fp32
  * x [nc][d][h][w] -> y [nc][sd][sh][sw]; backward by three separable gather passes (ws: *_bwd_ws_floats). */
 int u3d_upsample_trilinear(const float* x, long long nc, int d, int h, int w, int s, float* y, u3d_stream_t stream);

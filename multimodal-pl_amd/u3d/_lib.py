@@ -122,6 +122,10 @@ _SIGS = {
     "u3d_eam_attn_bwd_part_floats": [I, L, I, I],
     "u3d_eam_attn_bwd": [I, P, I, L, I, P, P, P, I, P, P, I, P, P, P, P, I, P],
     "u3d_eam_param_bwd": [P, I, I, P, P, P, P, P, P, F, P, P, P, P, P, P, I, P],
+    "u3d_eam_pool_blocks": [L],
+    "u3d_eam_pool_part_floats": [L, I, I],
+    "u3d_eam_pool_fwd": [I, P, I, L, I, P, P, P, I, I, F, P, P, P, P, P],
+    "u3d_eam_pool_bwd": [I, P, I, L, I, P, P, P, I, I, F, P, P, P, P, P, I, P, P, P, P, I, P],
     "u3d_upsample_trilinear": [P, L, I, I, I, I, P, P],
     "u3d_upsample_trilinear_bwd_ws_floats": [L, I, I, I, I],
     "u3d_upsample_trilinear_bwd": [P, L, I, I, I, I, P, I, P, P],
@@ -158,7 +162,7 @@ _SIGS = {
     "u3d_disc_side_wgrad": [I, P, P, I, I, P, I, I, I, I, I, I, I, P, P, P],
 }
 _RESTYPE = {"u3d_stem_fwd_ws_bytes": L, "u3d_stem1_stats_ws_floats": L, "u3d_conv_small_cnt_bytes": L, "u3d_conv_small_spart_floats": L, "u3d_conv_small_gb_parts_floats": L, "u3d_conv_s2_ring_ws_floats": L, "u3d_upsample2x_stats_ws_floats": L, "u3d_wstd_bwd_scratch_bytes": L, "u3d_gn_workspace_bytes": L, "u3d_channel_sum_workspace_bytes": L, "u3d_loss_workspace_bytes": L,
-            "u3d_eam_attn_bwd_part_floats": L, "u3d_upsample_trilinear_bwd_ws_floats": L, "u3d_renew_token_ws_bytes": L,
+            "u3d_eam_attn_bwd_part_floats": L, "u3d_eam_pool_part_floats": L,"u3d_upsample_trilinear_bwd_ws_floats": L, "u3d_renew_token_ws_bytes": L,
             "u3d_consistency_ws_bytes": L, "u3d_volume_stats_ws_bytes": L, "u3d_convg_brick_stats_ws_floats": L,
             "u3d_deepsup_loss_workspace_bytes": L, "u3d_disc_conv_fwd_ws_bytes": L, "u3d_disc_conv_wgrad_ws_bytes": L,
             "u3d_disc_bias_grad_ws_bytes": L, "u3d_disc_first_wgrad_ws_bytes": L, "u3d_disc_side_wgrad_ws_bytes": L}

@@ -11,8 +11,13 @@ Backward: every output gradient that autograd hands in (unused outputs arrive as
 through the same kernels' backward (u3d_upsample_trilinear_bwd, u3d_eam_attn_bwd, u3d_eam_param_bwd, the 1^3 head
 backward), accumulated into the decoder features' gradients, then the trunk tape replays.
 renew_token (:1051-1068) is u3d_renew_token on the stored features, in place on the device class tokens.
+
+unet3D_with_eam / unet3D_with_eam_baseline (:431-582, :1370-1504) run the whole EAM (eam_pool_op: the score map and
+the class message cm, u3d_eam_pool_fwd / _bwd) in a cascade down the decoder, each level's cm through a Linear the
+next level's token (run_eam); unet3D_with_feam (:1193-1367) is run_feam3 without the deep heads.
 """
 import torch
+import torch.nn.functional as F
 
 from . import ops, trunk
 from ._lib import call, query
@@ -105,18 +110,227 @@ def eam_op(tape, f, key, token, up):
     return out
 
 
-def _feam3_forward(tape, cfg, x, tokens, use_cm, deep_up, heads=True, renew=None, store=True):
+class Tok:
+    """A token-side value [nt, c] (fp32, outside autograd) and its accumulated gradient: the class token, a level's
+    class message, the Linear that hands it to the next level."""
+    __slots__ = ("t", "grad")
+
+    def __init__(self, t):
+        self.t = t
+        self.grad = None
+
+    def acc(self, g):
+        self.grad = g if self.grad is None else self.grad + g
+
+
+def _pool_before(tok, g3, b3, wq, wk):
+    """Token side before the voxel pass: z = LN3(tok), q = z Wq^T, A[i nt + t] = q[t, head i] Wk[head i, :]."""
+    c = tok.shape[1]
+    hd = c // NUM_HEADS
+    q = F.layer_norm(tok, (c,), g3, b3, 1e-5) @ wq.t()
+    return torch.cat([q[:, i * hd:(i + 1) * hd] @ wk[i * hd:(i + 1) * hd] for i in range(NUM_HEADS)], 0)
+
+
+def _pool_after(yhat, g2, b2, wv, pw, pb):
+    """Token side after it: Y = Yhat g2 + b2 (the softmax sums to 1), O[t, head i] = Wv[head i, :] . Y[i nt + t],
+    cm = proj(norm2(O)) + O (norm2 a second time, unet3D.py:206)."""
+    c = yhat.shape[1]
+    hd, nt = c // NUM_HEADS, yhat.shape[0] // NUM_HEADS
+    y = yhat * g2 + b2
+    o = torch.cat([y[i * nt:(i + 1) * nt] @ wv[i * hd:(i + 1) * hd].t() for i in range(NUM_HEADS)], 1)
+    return F.linear(F.layer_norm(o, (c,), g2, b2, 1e-5), pw, pb) + o
+
+
+def _leaves(*ts):
+    return [t.detach().requires_grad_(True) for t in ts]
+
+
+def _param_grads(tape, named):
+    """Hand finished parameter gradients [(name, parameter, gradient)] to the tape (a DDP bucket view or a tensor)."""
+    for name, p, g in named:
+        tape.grad_out(name, p).copy_(g)
+        tape.grad_done(name)
+
+
+def eam_pool_op(tape, f, key, tok):
+    """The whole EAM (unet3D.py:186-212) of decoder feature ``f`` (Act, NDHWC, batch 1) against ``tok`` (Tok [nt, C],
+    not detached) -> (Act holding the head-mean score map [1, nt, d, h, w], NCDHW fp32; Tok holding the class message
+    cm [nt, C]). The voxel side is u3d_eam_pool_fwd / _bwd: scores, softmax over all voxels and the pooling in one pass
+    over the feature, no k / v projection formed. The token side (<= 16 x 128: LN3, q, A before; Y, O, proj(norm2) +
+    residual after) is torch device operations, differentiated inside the backward closure by a local graph."""
+    P = tape.P
+    x = f.t
+    n, d, h, w, c = x.shape
+    v = d * h * w
+    if n != 1:
+        raise _eam_shape_error(n, v, c)
+    nt = tok.t.shape[0]
+    rows = NUM_HEADS * nt
+    scale = float((c // NUM_HEADS) ** -0.5)
+    dev = x.device
+    names = [key + s for s in (".kv.weight", ".q.weight", ".proj.weight", ".proj.bias", ".norm2.weight", ".norm2.bias",
+                               ".norm3.weight", ".norm3.bias")]
+    kv, wq, pw, pb, g2, b2, g3, b3 = (P[nm] for nm in names)
+    new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)   # noqa: E731
+    with torch.no_grad():
+        A = _pool_before(tok.t, g3, b3, wq, kv[:c]).contiguous()
+    att, yhat, stat = new(n, nt, d, h, w), new(rows, c), new(2 * rows)
+    npart = query("u3d_eam_pool_part_floats", v, c, nt)
+    call("u3d_eam_pool_fwd", ops.dt_code(x.dtype), x.data_ptr(), n, v, c, g2.data_ptr(), b2.data_ptr(), A.data_ptr(), nt,
+         NUM_HEADS, scale, att.data_ptr(), yhat.data_ptr(), stat.data_ptr(), new(npart).data_ptr(), ops._stream())
+    with torch.no_grad():
+        cm = Tok(_pool_after(yhat, g2, b2, kv[c:], pw, pb))
+    out = trunk.Act(att)
+    if tape.record:
+        def bwd():
+            gatt, gcm = out.grad, cm.grad
+            if gatt is None and gcm is None:
+                return
+            pg = {}
+            dy = dd = None
+            if gcm is not None:      # cm -> dYhat and the token-side halves of norm2, kv (v rows), proj
+                with torch.enable_grad():
+                    lv = _leaves(yhat, g2, b2, kv, pw, pb)
+                    gs = torch.autograd.grad(_pool_after(lv[0], lv[1], lv[2], lv[3][c:], lv[4], lv[5]), lv, gcm)
+                dy = gs[0].contiguous()
+                dd = (dy * yhat).sum(1)
+                pg.update(zip((names[4], names[5], names[0], names[2], names[3]), gs[1:]))
+            if gatt is not None:
+                gatt = gatt.float().contiguous()
+            dA, dg2, db2 = new(rows, c), new(c), new(c)
+            acc = f.grad is not None
+            dx = f.grad if acc else torch.empty_like(x)
+            ptr = lambda t: t.data_ptr() if t is not None else 0       # noqa: E731
+            call("u3d_eam_pool_bwd", ops.dt_code(x.dtype), x.data_ptr(), n, v, c, g2.data_ptr(), b2.data_ptr(),
+                 A.data_ptr(), nt, NUM_HEADS, scale, stat.data_ptr(), ptr(dy), ptr(dd), ptr(gatt), dx.data_ptr(),
+                 int(acc), new(npart).data_ptr(), dA.data_ptr(), dg2.data_ptr(), db2.data_ptr(), 0, ops._stream())
+            f.grad = dx
+            with torch.enable_grad():  # dA -> the token, norm3, q and the k rows of kv
+                lv = _leaves(tok.t, g3, b3, wq, kv)
+                gs = torch.autograd.grad(_pool_before(lv[0], lv[1], lv[2], lv[3], lv[4][:c]), lv, dA)
+            tok.acc(gs[0])
+            for nm, g in ((names[4], dg2), (names[5], db2), (names[6], gs[1]), (names[7], gs[2]), (names[1], gs[3]),
+                          (names[0], gs[4])):
+                pg[nm] = pg[nm] + g if nm in pg else g
+            _param_grads(tape, [(nm, P[nm], g) for nm, g in pg.items()])
+        tape.ops.append(bwd)
+    return out, cm
+
+
+def tok_linear(tape, tok, key):
+    """nn.Linear on a class message (linear84_2_42 / linear42_2_21, unet3D.py:552, :564): Tok [nt, cin] -> Tok [nt, cout]."""
+    W, b = tape.P[key + ".weight"], tape.P[key + ".bias"]
+    with torch.no_grad():
+        out = Tok(torch.addmm(b, tok.t, W.t()))
+    if tape.record:
+        def bwd():
+            g = out.grad
+            if g is None:
+                return
+            _param_grads(tape, [(key + ".weight", W, g.t() @ tok.t), (key + ".bias", b, g.sum(0))])
+            tok.acc(g @ W)
+        tape.ops.append(bwd)
+    return out
+
+
+EAM_LINEAR_KEYS = ("linear84_2_42", "linear42_2_21")
+
+
+def _eam_forward(tape, cfg, x, gates, train):
+    """unet3D_with_eam / _eam_baseline (unet3D.py:508-582, :1440-1504): the trunk, and in training the cascade of EAMs
+    down the decoder, each level's class message through a Linear the next level's token. gates[k]: level k runs (the
+    reference's cumulative use_cm tests). Returns (logits Act, last cm Tok or None, [map Act])."""
+    root = None
+    if train and gates[0]:
+        root = Tok(tape.P["class_token"].detach())
+        if tape.record:
+            def bwd():   # recorded first, so it runs last: every level has added its share by then
+                if root.grad is not None:
+                    _param_grads(tape, [("class_token", tape.P["class_token"], root.grad)])
+            tape.ops.append(bwd)
+    f, _ = tape.trunk(x, cfg)
+    lg = tape.head(f, cfg)
+    cm, att = None, []
+    for k, on in enumerate(gates):
+        if not (train and on):
+            break
+        tok = root if k == 0 else tok_linear(tape, cm, EAM_LINEAR_KEYS[k - 1])
+        a, cm = eam_pool_op(tape, tape.dec[k], EAM_KEYS[k], tok)
+        att.append(a)
+    return lg, cm, att
+
+
+class _EamFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, cfg, dtype, gates, names, x, *tensors):
+        ctx.set_materialize_grads(False)
+        tape = trunk.Tape(dict(zip(names, tensors)), dtype, record=True)
+        tape.sink = current_sink()
+        if tape.sink is not None:
+            tape.sink.begin()
+        lg, cm, att = _eam_forward(tape, cfg, x, gates, True)
+        ctx.state = (tape, lg, cm, att)
+        ctx.names = names
+        return tuple([_ncdhw(lg.t)] + ([cm.t.unsqueeze(0)] if cm is not None else []) + [a.t for a in att])
+
+    @staticmethod
+    def backward(ctx, *grads):
+        tape, lg, cm, att = ctx.state
+        g_lg = grads[0]
+        if cm is not None:
+            cm.grad = grads[1].reshape(cm.t.shape).float() if grads[1] is not None else None
+            for a, g in zip(att, grads[2:]):
+                a.grad = g.contiguous() if g is not None else None
+        if g_lg is None:
+            g_lg = torch.zeros(lg.t.shape, dtype=torch.float32, device=lg.t.device)
+        else:
+            g_lg = g_lg.permute(0, 2, 3, 4, 1).float().contiguous()
+        tape.backward(lg, g_lg)
+        if tape.sink is not None:
+            tape.sink.finish()
+        pg = [tape.pgrad.get(nm) for nm in ctx.names]
+        if tape.sink is not None:
+            pg = tape.sink.returned(ctx.names, pg)
+        ctx.state = None
+        return (None, None, None, None, None, *pg)
+
+
+def run_eam(model, x, gates):
+    """model: unet3D.unet3D_with_eam / unet3D_with_eam_baseline. train: (logits, cm [1, nt, C] or None, atten_map);
+    eval: logits (the EAMs are not run)."""
+    ops.require_device(x)
+    cfg = model._u3d_cfg
+    dtype = trunk.compute_dtype(getattr(model, "compute_dtype", None))
+    x = x.float().contiguous()
+    named = list(model.named_parameters())
+    gates = tuple(bool(g) for g in gates)
+    if model.training and torch.is_grad_enabled() and any(p.requires_grad for _, p in named):
+        outs = _EamFn.apply(cfg, dtype, gates, [nm for nm, _ in named], x, *[p for _, p in named])
+        if not gates[0]:
+            return outs[0], None, []
+        return outs[0], outs[1], list(outs[2:])
+    with torch.no_grad():
+        tape = trunk.Tape(dict(named), dtype, record=False)
+        lg, cm, att = _eam_forward(tape, cfg, x, gates, model.training)
+    if not model.training:
+        return _ncdhw(lg.t)
+    return _ncdhw(lg.t), cm.t.unsqueeze(0) if cm is not None else None, [a.t for a in att]
+
+
+def _feam3_forward(tape, cfg, x, tokens, use_cm, deep_up, heads=True, renew=None, store=True, deep_heads=True):
     """renew = (mask, num_classes, alpha): unet3D_with_feam2's in-forward class-token update of each level, before
     that level's attention (unet3D.py:869-878, 896-903, 919-926). store=False: no detached feature copies
-    (unet3D_with_deepsup, unet3D.py:370-429: the trunk and the three deep-supervision heads alone)."""
+    (unet3D_with_deepsup, unet3D.py:370-429: the trunk and the three deep-supervision heads alone). deep_heads=False:
+    no deepout heads (unet3D_with_feam, unet3D.py:1272-1367: the renewed tokens and the attention maps alone)."""
     f, _ = tape.trunk(x, cfg)
     lg = tape.head(f, cfg)
     att, deep, feats = [], [], []
     if heads:
         for k in range(3):
             fk = tape.dec[k]
-            deep.append(tape.gn_conv(fk, f"deepout{k + 1}.2", 1, 1, gn_key=f"deepout{k + 1}.0", G=16, bias=True,
-                                     out_f32=True, standardize=False))
+            if deep_heads:
+                deep.append(tape.gn_conv(fk, f"deepout{k + 1}.2", 1, 1, gn_key=f"deepout{k + 1}.0", G=16, bias=True,
+                                         out_f32=True, standardize=False))
             if store:
                 feats.append(fk.t.detach().clone())
             if renew is not None:
@@ -132,14 +346,15 @@ def _ncdhw(t):
 
 class _Feam3Fn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, cfg, dtype, use_cm, deep_up, store, names, x, tokens, *tensors):
+    def forward(ctx, cfg, dtype, use_cm, deep_up, store, deep_heads, names, x, tokens, *tensors):
         ctx.set_materialize_grads(False)
         P = dict(zip(names, tensors))
         tape = trunk.Tape(P, dtype, record=True)
         tape.sink = current_sink()
         if tape.sink is not None:
             tape.sink.begin()
-        lg, att, deep, feats = _feam3_forward(tape, cfg, x, tokens, use_cm, deep_up, store=store)
+        lg, att, deep, feats = _feam3_forward(tape, cfg, x, tokens, use_cm, deep_up, store=store,
+                                              deep_heads=deep_heads)
         ctx.state = (tape, lg, att, deep)
         ctx.names = names
         ctx.n_att = len(att)
@@ -154,7 +369,7 @@ class _Feam3Fn(torch.autograd.Function):
         g_lg = grads[0]
         for a, g in zip(att, grads[1:1 + na]):
             a.grad = g.contiguous() if g is not None else None
-        for d, g in zip(deep, grads[1 + na:4 + na]):
+        for d, g in zip(deep, grads[1 + na:1 + na + len(deep)]):
             d.grad = g.permute(0, 2, 3, 4, 1).float().contiguous() if g is not None else None
         if g_lg is None:
             g_lg = torch.zeros(lg.t.shape, dtype=torch.float32, device=lg.t.device)
@@ -167,19 +382,30 @@ class _Feam3Fn(torch.autograd.Function):
         if tape.sink is not None:
             pg = tape.sink.returned(ctx.names, pg)
         ctx.state = None
-        return (None, None, None, None, None, None, None, None, *pg)
+        return (None, None, None, None, None, None, None, None, None, *pg)
 
 
-def run_feam3(model, x, renew=None, eam=True):
+def labels_reach(mask, sizes, ncls):
+    """True when a label 1..ncls of ``mask`` [n, 1, D, H, W] survives the nearest resize to one of ``sizes``: the
+    condition under which the reference's in-forward token renewal writes a token (unet3D.py:1301-1308). One host
+    synchronisation; callers ask only where the answer decides between an error and a gradient run."""
+    valid = ((mask >= 1) & (mask <= ncls) & (mask == mask.floor())).float()
+    return any(bool(F.interpolate(valid, s, mode="nearest").any()) for s in sizes)
+
+
+def run_feam3(model, x, renew=None, eam=True, deep_heads=True, gates=None):
     """model: unet3D.unet3D_with_feam3 (or _feam2). Returns train: (logits, atten_map, deep_map, feature_stored);
     eval: logits. eam=False: unet3D.unet3D_with_deepsup, the same graph without the EAMs, the class tokens and the
-    stored features (atten_map and feature_stored come back empty; any batch size)."""
+    stored features (atten_map and feature_stored come back empty; any batch size). deep_heads=False:
+    unet3D.unet3D_with_feam, no deepout heads and no stored features (deep_map and feature_stored come back empty);
+    gates: which levels run their EAM, instead of model.use_cm (the reference's cumulative tests there)."""
     ops.require_device(x)
     cfg = model._u3d_cfg
     dtype = trunk.compute_dtype(getattr(model, "compute_dtype", None))
     x = x.float().contiguous()
     tokens = [model.class_token1, model.class_token2, model.class_token3] if eam else None
-    use_cm = tuple(bool(u) and eam for u in model.use_cm)
+    use_cm = tuple(bool(u) and eam for u in (model.use_cm if gates is None else gates))
+    store, nd = eam and deep_heads, 3 if deep_heads else 0
     deep_up = bool(eam and model.deep_up)
     named = list(model.named_parameters())
     if not model.training:
@@ -190,15 +416,16 @@ def run_feam3(model, x, renew=None, eam=True):
     if torch.is_grad_enabled() and any(p.requires_grad for _, p in named):
         if renew is not None:
             raise RuntimeError("a leaf Variable that requires grad is being used in an in-place operation.")
-        outs = _Feam3Fn.apply(cfg, dtype, use_cm, deep_up, eam, [nm for nm, _ in named], x, tokens,
+        outs = _Feam3Fn.apply(cfg, dtype, use_cm, deep_up, store, deep_heads, [nm for nm, _ in named], x, tokens,
                               *[p for _, p in named])
     else:
         with torch.no_grad():
             tape = trunk.Tape(dict(named), dtype, record=False)
-            lg, att, deep, feats = _feam3_forward(tape, cfg, x, tokens, use_cm, deep_up, renew=renew, store=eam)
+            lg, att, deep, feats = _feam3_forward(tape, cfg, x, tokens, use_cm, deep_up, renew=renew, store=store,
+                                                  deep_heads=deep_heads)
         outs = [_ncdhw(lg.t)] + [a.t for a in att] + [_ncdhw(d.t) for d in deep] + [_ncdhw(ft) for ft in feats]
     na = sum(use_cm)
-    return outs[0], list(outs[1:1 + na]), list(outs[1 + na:4 + na]), list(outs[4 + na:])
+    return outs[0], list(outs[1:1 + na]), list(outs[1 + na:1 + na + nd]), list(outs[1 + na + nd:])
 
 
 def renew_token(tokens, features, mask, num_classes, alpha):

@@ -222,8 +222,9 @@ def _next_row(name, row):
 
 
 class EAM(nn.Module):
-    """Reference unet3D.py:142-212 (same parameters: kv, q, proj, norm2, norm3). Inside unet3D_with_feam3 its
-    attention map runs natively (u3d.feam: only ``attn`` is used there, :1134); called on its own it raises."""
+    """Reference unet3D.py:142-212 (same parameters: kv, q, proj, norm2, norm3). Inside unet3D_with_feam3 / _feam2 /
+    _feam its attention map runs natively (u3d.feam.eam_op: only ``attn`` is used there, :1134), inside
+    unet3D_with_eam / _eam_baseline the whole module does (u3d.feam.eam_pool_op); called on its own it raises."""
 
     def __init__(self, dim, input_resolution, num_heads, mlp_ratio=4., qkv_bias=True, qk_scale=None, drop=0.,
                  attn_drop=0., drop_path=0., norm_layer=nn.LayerNorm, upsample=None, use_checkpoint=False):
@@ -375,11 +376,130 @@ class unet3D_with_deepsup(_TrunkMixin, nn.Module):
         return outs
 
 
-# Method-specific variants: next rows, not on the trunk path. get_style_discriminator (a
-# (2, 3, 2) conv) is not built by the driver.
-unet3D_with_feam = _next_row("unet3D_with_feam", "f2")
-unet3D_with_eam = _next_row("unet3D_with_eam", "f2")
-unet3D_with_eam_baseline = _next_row("unet3D_with_eam_baseline", "f2")
+def _build_eam_trunk(self, layers, num_classes, eams, linears):
+    """The modules of unet3D_with_eam (:439-475), unet3D_with_eam_baseline (:1377-1412) and unet3D_with_feam
+    (:1201-1235) in the reference's registration order: the trunk with an EAM after x8 / x4 / x2_resb (the first
+    ``eams`` of them) and, after the first ``linears`` EAMs, the Linear that hands the class message down a level."""
+    mk = lambda cin, cout, n, s: _make_layer(self, NoBottleneck, cin, cout, n, stride=s)  # noqa: E731
+    self.conv1 = conv3x3x3(1, 32, stride=[1, 1, 1], weight_std=self.weight_std)
+    self.layer0 = mk(32, 32, layers[0], (1, 1, 1))
+    self.layer1 = mk(32, 64, layers[1], (2, 2, 2))
+    self.layer2 = mk(64, 128, layers[2], (2, 2, 2))
+    self.layer3 = mk(128, 256, layers[3], (2, 2, 2))
+    self.layer4 = mk(256, 256, layers[4], (2, 2, 2))
+    self.fusionConv = nn.Sequential(
+        nn.GroupNorm(16, 256), nn.ReLU(inplace=in_place),
+        conv3x3x3(256, 256, kernel_size=(1, 1, 1), padding=(0, 0, 0), weight_std=self.weight_std))
+    self.upsamplex2 = nn.Upsample(scale_factor=2, mode="trilinear")
+    for k, (name, cin, cout, ekey, lkey) in enumerate((("x8_resb", 256, 128, "eam84", "linear84_2_42"),
+                                                       ("x4_resb", 128, 64, "eam42", "linear42_2_21"),
+                                                       ("x2_resb", 64, 32, "eam21", None))):
+        setattr(self, name, mk(cin, cout, 1, (1, 1, 1)))
+        if k < eams:
+            setattr(self, ekey, EAM(cout, input_resolution=None, num_heads=4))
+        if k < linears:
+            setattr(self, lkey, nn.Linear(cout, cout // 2))
+    self.x1_resb = mk(32, 32, 1, (1, 1, 1))
+    self.precls_conv = nn.Sequential(nn.GroupNorm(16, 32), nn.ReLU(inplace=in_place),
+                                     nn.Conv3d(32, num_classes, kernel_size=1))
+    self._u3d_cfg = trunk.TrunkCfg(layers=tuple(layers), weight_std=bool(self.weight_std))
+
+
+def _cascade(use_cm, n):
+    """The reference's cumulative tests: level k runs when use_cm[0] .. use_cm[k] all hold (unet3D.py:536, 551, 563)."""
+    return [all(bool(u) for u in use_cm[:k + 1]) for k in range(n)]
+
+
+class unet3D_with_eam(_TrunkMixin, nn.Module):
+    """Reference unet3D.py:431-582 (the model evaluate_amos.py:574 builds): the trunk + a cascade of whole EAMs. The
+    class token [num_classes, 128] is a Parameter and is not detached; each level's class message cm goes through a
+    Linear and is the next level's token. forward(input, task_id) -> train: (logits, cm [1, num_classes, C of the last
+    level run], atten_map); eval: logits (the EAMs are not run). Batch 1, as the reference's EAM reshape demands;
+    with use_cm[0] false a train forward fails as the reference's does, on the cm it never made."""
+
+    def __init__(self, layers, num_classes=12, weight_std=False, ema=False, use_cm=[True, True, True]):  # noqa: B006
+        self.inplanes = 128
+        self.weight_std = weight_std
+        self.num_classes = num_classes
+        self.use_cm = use_cm
+        super().__init__()
+        _build_eam_trunk(self, layers, num_classes, eams=3, linears=2)
+        self.class_token = nn.Parameter(torch.randn(num_classes, 128))
+        if ema:
+            for param in self.parameters():
+                param.detach_()
+
+    def _gates(self):
+        return _cascade(self.use_cm, 3)
+
+    def forward(self, input, task_id=None):
+        from u3d import feam
+        gates = self._gates()
+        if self.training and not gates[0]:
+            feam.ops.require_device(input)
+            raise UnboundLocalError("local variable 'cm' referenced before assignment")  # unet3D.py:580
+        return feam.run_eam(self, input, gates)
+
+
+class unet3D_with_eam_baseline(unet3D_with_eam):
+    """Reference unet3D.py:1370-1504: two EAM levels (eam84 -> linear84_2_42 -> eam42), always on; cm is eam42's."""
+
+    def __init__(self, layers, num_classes=12, weight_std=False):
+        self.inplanes = 128
+        self.weight_std = weight_std
+        self.num_classes = num_classes
+        nn.Module.__init__(self)
+        _build_eam_trunk(self, layers, num_classes, eams=2, linears=1)
+        self.class_token = nn.Parameter(torch.randn(num_classes, 128))
+
+    def _gates(self):
+        return [True, True]
+
+
+class unet3D_with_feam(_TrunkMixin, nn.Module):
+    """Reference unet3D.py:1193-1367: the trunk + EAM attention maps against Parameter class tokens that a train
+    forward renews from the labelled voxels (13 classes, factor 0.01) before each level's attention; no deep heads.
+    forward(input, mask=None) -> train: (logits, atten_map); eval: logits. The maps exist only in training, under the
+    reference's cumulative use_cm tests. As there, a label that reaches a level while the tokens require grad is an
+    in-place write autograd refuses (it works with ema=True, or with a mask that holds no label), and mask=None fails
+    at ``(mask == l+1)``."""
+    RENEW_CLASSES, ALPHA = 13, 0.01
+
+    def __init__(self, layers, num_classes=12, weight_std=False, ema=False, use_cm=[True, True, True]):  # noqa: B006
+        self.inplanes = 128
+        self.weight_std = weight_std
+        self.num_classes = num_classes
+        self.use_cm = use_cm
+        self.deep_up = False
+        super().__init__()
+        _build_eam_trunk(self, layers, num_classes, eams=3, linears=0)
+        self.class_token1 = nn.Parameter(torch.randn(num_classes - 1, 128))
+        self.class_token2 = nn.Parameter(torch.randn(num_classes - 1, 64))
+        self.class_token3 = nn.Parameter(torch.randn(num_classes - 1, 32))
+        if ema:
+            for param in self.parameters():
+                param.detach_()
+
+    def forward(self, input, mask=None):
+        from u3d import feam
+        gates = _cascade(self.use_cm, 3)
+        feam.ops.require_device(input)
+        if not self.training:
+            return feam.run_feam3(self, input, deep_heads=False, gates=gates)
+        if mask is None:
+            raise AttributeError("'bool' object has no attribute 'sum'")  # (None == l+1).sum(), unet3D.py:1302
+        feam.ops.require_device(mask)
+        renew = (mask, self.RENEW_CLASSES, self.ALPHA)
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            sizes = [tuple(s // f for s in input.shape[2:]) for f in (8, 4, 2)]
+            if feam.labels_reach(mask, sizes, self.RENEW_CLASSES):
+                raise RuntimeError("a leaf Variable that requires grad is being used in an in-place operation.")
+            renew = None   # no label reaches a level: the renewal writes nothing
+        outs = feam.run_feam3(self, input, renew=renew, deep_heads=False, gates=gates)
+        return outs[0], outs[1]
+
+
+# get_style_discriminator (a (2, 3, 2) conv) is not built by the driver: SURVEY.md §2, out of scope.
 get_style_discriminator = _next_row("get_style_discriminator", "out-of-scope")
 
 
