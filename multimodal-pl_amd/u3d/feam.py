@@ -21,7 +21,6 @@ import torch.nn.functional as F
 
 from . import ops, trunk
 from ._lib import call, query
-from .ddp import current_sink
 
 EAM_KEYS = ("eam84", "eam42", "eam21")
 UP_SCALE = (8, 4, 2)   # upsamplex4 / upsamplex3 / upsamplex2 for deep_up (:1138, :1156, :1175)
@@ -264,10 +263,7 @@ class _EamFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cfg, dtype, gates, names, x, *tensors):
         ctx.set_materialize_grads(False)
-        tape = trunk.Tape(dict(zip(names, tensors)), dtype, record=True)
-        tape.sink = current_sink()
-        if tape.sink is not None:
-            tape.sink.begin()
+        tape = trunk.Tape.recording(names, tensors, dtype)
         lg, cm, att = _eam_forward(tape, cfg, x, gates, True)
         ctx.state = (tape, lg, cm, att)
         ctx.names = names
@@ -281,16 +277,7 @@ class _EamFn(torch.autograd.Function):
             cm.grad = grads[1].reshape(cm.t.shape).float() if grads[1] is not None else None
             for a, g in zip(att, grads[2:]):
                 a.grad = g.contiguous() if g is not None else None
-        if g_lg is None:
-            g_lg = torch.zeros(lg.t.shape, dtype=torch.float32, device=lg.t.device)
-        else:
-            g_lg = g_lg.permute(0, 2, 3, 4, 1).float().contiguous()
-        tape.backward(lg, g_lg)
-        if tape.sink is not None:
-            tape.sink.finish()
-        pg = [tape.pgrad.get(nm) for nm in ctx.names]
-        if tape.sink is not None:
-            pg = tape.sink.returned(ctx.names, pg)
+        pg = _backward(tape, lg, g_lg, ctx.names)
         ctx.state = None
         return (None, None, None, None, None, *pg)
 
@@ -344,15 +331,21 @@ def _ncdhw(t):
     return t.permute(0, 4, 1, 2, 3)
 
 
+def _backward(tape, lg, g_lg, names):
+    """Replay ``tape`` from the logits' NCDHW gradient (None: no loss reads them, zeros) -> parameter gradients."""
+    if g_lg is None:
+        g_lg = torch.zeros(lg.t.shape, dtype=torch.float32, device=lg.t.device)
+    else:
+        g_lg = trunk.ndhwc_grad(g_lg)
+    tape.backward(lg, g_lg)
+    return tape.finish(names)
+
+
 class _Feam3Fn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cfg, dtype, use_cm, deep_up, store, deep_heads, names, x, tokens, *tensors):
         ctx.set_materialize_grads(False)
-        P = dict(zip(names, tensors))
-        tape = trunk.Tape(P, dtype, record=True)
-        tape.sink = current_sink()
-        if tape.sink is not None:
-            tape.sink.begin()
+        tape = trunk.Tape.recording(names, tensors, dtype)
         lg, att, deep, feats = _feam3_forward(tape, cfg, x, tokens, use_cm, deep_up, store=store,
                                               deep_heads=deep_heads)
         ctx.state = (tape, lg, att, deep)
@@ -370,17 +363,8 @@ class _Feam3Fn(torch.autograd.Function):
         for a, g in zip(att, grads[1:1 + na]):
             a.grad = g.contiguous() if g is not None else None
         for d, g in zip(deep, grads[1 + na:1 + na + len(deep)]):
-            d.grad = g.permute(0, 2, 3, 4, 1).float().contiguous() if g is not None else None
-        if g_lg is None:
-            g_lg = torch.zeros(lg.t.shape, dtype=torch.float32, device=lg.t.device)
-        else:
-            g_lg = g_lg.permute(0, 2, 3, 4, 1).float().contiguous()
-        tape.backward(lg, g_lg)
-        if tape.sink is not None:
-            tape.sink.finish()
-        pg = [tape.pgrad.get(nm) for nm in ctx.names]
-        if tape.sink is not None:
-            pg = tape.sink.returned(ctx.names, pg)
+            d.grad = trunk.ndhwc_grad(g) if g is not None else None
+        pg = _backward(tape, lg, g_lg, ctx.names)
         ctx.state = None
         return (None, None, None, None, None, None, None, None, None, *pg)
 

@@ -600,18 +600,29 @@ def conv_dgrad_gn(dy, wpk_dgrad, cin, x, k, stride, gn, dgb=None):
     caller then takes conv_dgrad + gn_bwd). On the small-volume kernel (and with ``dgb``, a callable returning the
     (dgamma, dbeta) destinations) the finalize runs inside the launch too: parts is then ("coef", coef) for
     gn_bwd_apply_coef, dgamma / dbeta already written."""
-    n, d, h, w_ = shape = tuple(x.shape[:4])
-    route = _route_dgrad(dy, cin, shape, k, stride)
-    if not (route == "ring32" and GN_BWD_FUSED and gn is not None and CONV32_FN == "u3d_conv32_ring"
+    return _dgrad_gn(_route_dgrad(dy, cin, x.shape[:4], k, stride), dy, wpk_dgrad, cin, x, k, stride, gn, dgb)
+
+
+def _dgrad_gn(route, dy, wpk_dgrad, cin, x, k, stride, gn, dgb):
+    """conv_dgrad_gn of a conv whose data gradient is routed to ``route``: the ring, small or brick fused form in that
+    order, or None. A launcher that declines (its ``made`` flag) falls through to the next form."""
+    if (route == "ring32" and GN_BWD_FUSED and gn is not None and CONV32_FN == "u3d_conv32_ring"
             and not _ring_queue(dgrad=True)):
-        # (where the ring runs without its own fused form, e.g. as the queue form under a collective, the small form
-        # still takes the volumes it would run were the ring not there; the brick form does not)
-        rs = route if route != "ring32" else _route_dgrad(dy, cin, shape, k, stride, skip="ring32")
-        r = None
-        if dgb is not None and _small_gb_ok(rs, x, cin):
-            ws = WS.get(SPLITK_WS_BYTES, dy.device, Slot.SPLITK)
-            r = _conv_dgrad_gn_small(dy, wpk_dgrad, cin, x, gn, dgb, ws)
-        return r if r is not None else _conv_dgrad_gn_brick(route, dy, wpk_dgrad, cin, x, gn)
+        return _conv_dgrad_gn_ring(dy, wpk_dgrad, cin, x, gn, dgb)
+    # (where the ring runs without its own fused form, e.g. as the queue form under a collective, the small form
+    # still takes the volumes it would run were the ring not there; the brick form does not)
+    rs = route if route != "ring32" else _route_dgrad(dy, cin, x.shape[:4], k, stride, skip="ring32")
+    r = None
+    if dgb is not None and _small_gb_ok(rs, x, cin):
+        ws = WS.get(SPLITK_WS_BYTES, dy.device, Slot.SPLITK)
+        r = _conv_dgrad_gn_small(dy, wpk_dgrad, cin, x, gn, dgb, ws)
+    return r if r is not None else _conv_dgrad_gn_brick(route, dy, wpk_dgrad, cin, x, gn)
+
+
+def _conv_dgrad_gn_ring(dy, wpk_dgrad, cin, x, gn, dgb):
+    """The ring32 family's data gradient with the GroupNorm-backward partials from its epilogue: (dA, parts), or with
+    FUSED_FINALIZE and ``dgb`` (dA, ("coef", coef))."""
+    n, d, h, w_ = shape = tuple(x.shape[:4])
     st, ga, be, G = gn
     wps = query("u3d_conv32_ring_wps", n, d, h, w_)
     da = torch.empty((n, d, h, w_, cin), dtype=dy.dtype, device=dy.device)
@@ -727,10 +738,10 @@ def s2_compact_ok(in_shape, cin, elsize):
     return d * h * w_ < (1 << 24) and n * cv * cin * elsize < (1 << 31)
 
 
-def s2_compact_dgrad_ok(dy, cin, in_shape):
-    """Whether conv_dgrad_1x1s2_compact serves a stride-2 1^3 conv's data gradient: S2_COMPACT, at the conv's output
-    resolution it is a stride-1 1^3 data gradient on the conv1x1 family, and s2_compact_ok's limits hold."""
-    return (S2_COMPACT and _route_dgrad(dy, cin, dy.shape[:4], 1, 1) == "conv1x1"
+def s2_compact_dgrad_ok(dy, cin, in_shape, k=1, stride=2):
+    """Whether conv_dgrad_1x1s2_compact serves a conv's data gradient: a stride-2 1^3 conv, S2_COMPACT, at the conv's
+    output resolution it is a stride-1 1^3 data gradient on the conv1x1 family, and s2_compact_ok's limits hold."""
+    return (k == 1 and stride == 2 and S2_COMPACT and _route_dgrad(dy, cin, dy.shape[:4], 1, 1) == "conv1x1"
             and s2_compact_ok(in_shape, cin, dy.element_size()))
 
 
@@ -757,23 +768,40 @@ WGRAD_QUEUE = os.environ.get("U3D_WGRAD_QUEUE", "0") != "0"
 WGRAD_Q_WGS = 768
 
 
-def _wgrad_route(dy, x, k, stride):
-    """The weight-gradient kernel family conv_wgrad picks: "ring", True (halo bricks / the 1^3 kernel) or False."""
+WGRAD_ROUTES = ("ring", "brick", "gemm")
+
+
+def wgrad_route(dy, x, k, stride):
+    """The weight-gradient kernel family (one of WGRAD_ROUTES) of one conv: the depth-streaming ring, "brick" (halo
+    bricks; at k = 1 the 1^3 kernel) or the implicit GEMM. Like conv_route, the only place that orders them."""
+    if not (USE_BRICK_WGRAD and x.dtype == torch.bfloat16):
+        return "gemm"
     h, w_ = x.shape[2], x.shape[3]
-    brick = USE_BRICK_WGRAD and x.dtype == torch.bfloat16
-    if (brick and k == 3 and stride == 1 and USE_RING_WGRAD and min(h, w_) >= RING_WGRAD_MIN_HW
+    if (k == 3 and stride == 1 and USE_RING_WGRAD and min(h, w_) >= RING_WGRAD_MIN_HW
             and max(x.numel() * x.element_size(), dy.numel() * dy.element_size()) < (1 << 31)):
-        brick = "ring"  # (the ring addresses its operands with 32-bit buffer offsets; larger ones: bricks)
-    return brick
+        return "ring"  # (the ring addresses its operands with 32-bit buffer offsets; larger ones: bricks)
+    return "brick"
+
+
+_WGRAD_FORMER = {True: "brick", False: "gemm"}  # brick= values from before WGRAD_ROUTES: callers that still pass them
+
+
+def _wgrad_route(dy, x, k, stride):
+    """wgrad_route under its former name and values ("ring", True, False), for callers written before WGRAD_ROUTES."""
+    r = wgrad_route(dy, x, k, stride)
+    return r if r == "ring" else r == "brick"
 
 
 def conv_wgrad(dy, x, k, stride, gn=None, brick=None):
-    """Returns (partials fp32 [nsplit, k^3, cout_p, cin_p], nsplit). bf16 3^3 convs use the halo-brick kernel."""
+    """Returns (partials fp32 [nsplit, k^3, cout_p, cin_p], nsplit). ``brick``: the conv's WGRAD_ROUTES name where the
+    caller has routed it already (or forces a family); True / False still mean "brick" / "gemm"."""
     n, d, h, w_, cin = x.shape
     cout = dy.shape[-1]
     st, ga, be, G = _gn4(gn)
     if brick is None:
-        brick = _wgrad_route(dy, x, k, stride)
+        brick = wgrad_route(dy, x, k, stride)
+    elif (brick := _WGRAD_FORMER.get(brick, brick)) not in WGRAD_ROUTES:
+        raise _lib.U3DError(f"u3d: conv_wgrad(brick={brick!r}): not one of {WGRAD_ROUTES}")
     if brick == "ring":
         assert k == 3 and stride == 1 and x.dtype == torch.bfloat16
         if WGRAD_QUEUE or collective_in_flight():  # short ranges the dispatcher deals to whichever CU is free
@@ -786,7 +814,7 @@ def conv_wgrad(dy, x, k, stride, gn=None, brick=None):
              G, part.data_ptr(), ns, _stream())
         _probe1(pr, f"wgrad_ring {cin}->{cout}" + (" GN" if st is not None else ""), (n, d, h, w_), cin, cout)
         return part, ns
-    if brick:  # the 1^3 kernel, or halo bricks
+    if brick == "brick":  # the 1^3 kernel, or halo bricks
         fn, taps = ("u3d_conv_wgrad1", 1) if k == 1 else ("u3d_conv_wgrad_brick", 27)
         ns = query(fn + "_splits", n, cin, d, h, w_, cout, stride)
         part = torch.empty((ns, taps, round32(cout), round32(cin)), dtype=torch.float32, device=x.device)
@@ -813,16 +841,21 @@ def conv_bwd_pair_small(dy, pd, x, k, stride, gn, dgb):
     first runs the 12 x 12-tile ring or the 3 x 8 x 16 brick and the second the small family with the finalize inside
     (_small_gb_ok): returns (part, ns, dA, ("coef", coef)), or None (nothing launched, no output touched: the caller
     takes the two calls). Off while a collective is in flight: the DDP-tolerant weight gradient splits differently."""
-    if not (SMALL_BWD_PAIR and gn is not None and not collective_in_flight() and not WGRAD_QUEUE
-            and x.dim() == 5 and dy.dim() == 5):
+    if x.dim() != 5 or dy.dim() != 5:
         return None
+    return _bwd_pair_small(_route_dgrad(dy, x.shape[-1], x.shape[:4], k, stride), wgrad_route(dy, x, k, stride),
+                           dy, pd, x, gn, dgb)
+
+
+def _bwd_pair_small(route, wroute, dy, pd, x, gn, dgb):
+    """conv_bwd_pair_small of a conv whose gradients are routed to ``route`` (data) and ``wroute`` (weight)."""
     n, d, h, w_, cin = x.shape
     cout = dy.shape[-1]
-    if not _small_gb_ok(_route_dgrad(dy, cin, (n, d, h, w_), k, stride), x, cin):
+    if not (SMALL_BWD_PAIR and gn is not None and not collective_in_flight() and not WGRAD_QUEUE
+            and _small_gb_ok(route, x, cin) and wroute != "gemm"):
         return None
-    wroute = _wgrad_route(dy, x, k, stride)
-    if not wroute or (os.environ.get("U3D_LIB") and not hasattr(_lib.lib(), "u3d_conv_small_bwd_pair")):
-        return None  # (the latter: an A/B build of an older tree, _lib.lib)
+    if os.environ.get("U3D_LIB") and not hasattr(_lib.lib(), "u3d_conv_small_bwd_pair"):
+        return None  # (an A/B build of an older tree, _lib.lib)
     ring = int(wroute == "ring")
     ws = WS.get(SPLITK_WS_BYTES, dy.device, Slot.SPLITK)
     ns = query("u3d_conv_small_bwd_pair_ok", n, cout, d, h, w_, cin, ring, ws.numel())
@@ -846,6 +879,43 @@ def sum_slabs(part, ns, cout, cin):
     if ns > 1:
         call("u3d_wgrad_sum_slabs", part.data_ptr(), ns, part.shape[1], cout, cin, _stream())
     return part, 1
+
+
+def conv_bwd(dy, pd, x, cout, k, stride, gn, dgb, xn=None, want_da=True, fuse_gn=True, compact=False, wgrad_done=None):
+    """Both gradients of conv(relu(gn(x))) (``cout`` channels; dy may carry them padded to 8) for the tape, each routed
+    once (conv_route, wgrad_route) and the routes handed down: the 12^3 / 6^3 pair; else the weight gradient (on ``xn``
+    = relu(gn(x)) without a prologue where the forward stored it), its slabs summed under EAGER_SLAB_SUM, then the data
+    gradient with the GroupNorm backward's partials (_dgrad_gn), else the plain one. ``wgrad_done(part, ns)`` is
+    called once the weight gradient is launched, before the data gradient. ``want_da`` False: the caller has its dA
+    (the head's pass). ``fuse_gn`` False: this GroupNorm's backward runs paired with another, no partials; ``compact``:
+    the caller also takes a stride-2 1^3 conv's dA at the conv's output resolution (s2_compact_dgrad_ok).
+    Returns (dA, parts, compact): parts is None, the partials for gn_bwd_parts, or ("coef", coef) for
+    gn_bwd_apply_coef; compact says which resolution dA has."""
+    cin = x.shape[-1]
+    compact = compact and want_da and s2_compact_dgrad_ok(dy, cin, x.shape, k, stride)  # (routes the conv it becomes)
+    route = _route_dgrad(dy, cin, x.shape[:4], k, stride) if want_da and not compact else None
+    wroute = wgrad_route(dy, x, k, stride)
+    fuse_gn = fuse_gn and route is not None and gn is not None
+    r = _bwd_pair_small(route, wroute, dy, pd, x, gn, dgb) if fuse_gn and xn is None else None
+    if r is not None:
+        part, ns = r[:2]
+    elif xn is not None:
+        part, ns = conv_wgrad(dy, xn, k, stride, None, wroute)
+    else:
+        part, ns = conv_wgrad(dy, x, k, stride, gn, wroute)
+    if EAGER_SLAB_SUM and ns >= EAGER_SLAB_MIN:
+        part, ns = sum_slabs(part, ns, cout, cin)
+    if wgrad_done is not None:
+        wgrad_done(part, ns)
+    if r is not None:
+        return r[2], r[3], False
+    if compact:
+        return conv_dgrad_1x1s2_compact(dy, pd, cin), None, True
+    if route is None:
+        return None, None, False
+    if fuse_gn:
+        r = _dgrad_gn(route, dy, pd, cin, x, k, stride, gn, dgb)  # GN-backward partials in the epilogue
+    return (*r, False) if r is not None else (conv_dgrad(dy, pd, cin, x.shape[:4], k, stride, route), None, False)
 
 
 USE_HEAD = True

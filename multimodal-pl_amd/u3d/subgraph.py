@@ -3,7 +3,7 @@ executor when a caller uses that module on its own, outside the full trunk."""
 import torch
 
 from . import ops
-from .trunk import Act, Tape, compute_dtype
+from .trunk import Act, Tape, compute_dtype, ndhwc_grad
 
 
 class _SubFn(torch.autograd.Function):
@@ -11,7 +11,7 @@ class _SubFn(torch.autograd.Function):
     def forward(ctx, builder, dtype, std, names, x, *tensors):
         tape = Tape(dict(zip(names, tensors)), dtype, record=True)
         tape.std = std
-        xa = Act(x.permute(0, 2, 3, 4, 1).contiguous().to(dtype))
+        xa = Act(ndhwc_grad(x, dtype))
         out = builder(tape, xa)
         ctx.tape, ctx.xa, ctx.out, ctx.names = tape, xa, out, names
         return out.t.permute(0, 4, 1, 2, 3).float()
@@ -19,8 +19,7 @@ class _SubFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         tape = ctx.tape
-        g = g.permute(0, 2, 3, 4, 1).contiguous().to(ctx.out.t.dtype)
-        tape.backward(ctx.out, g)
+        tape.backward(ctx.out, ndhwc_grad(g, ctx.out.t.dtype))
         dx = ctx.xa.grad
         dx = dx.float().permute(0, 4, 1, 2, 3) if dx is not None else None
         grads = [tape.pgrad.get(n) for n in ctx.names]

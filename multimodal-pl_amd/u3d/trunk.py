@@ -8,6 +8,7 @@ Graph (reference unet3D.forward :1734-1806 / unet3D_baseline.forward :663-718 / 
   -> 4 x [trilinear x2 + skip -> x{8,4,2,1}_resb] -> precls_conv (GN,ReLU,1^3+bias) [-> x2 upsample (unet3D_g)]
 """
 from dataclasses import dataclass
+from functools import partial
 
 import torch
 
@@ -34,7 +35,7 @@ class Act:
         self.t = t
         self.stats = {}
         self.grad = None
-        self.gn_pend = None  # the parked (dA, gn, key, compact) of a block's downsample GN until gn1's backward fuses both
+        self.gn_pend = None  # the parked (dA, gn, key, compact) of a block's downsample GN (Tape.prologue_bwd)
 
 
 class Tape:
@@ -48,6 +49,23 @@ class Tape:
         self.sink = None
         self.std = True
         self.pending = []   # weight grads waiting for the batched standardisation backward
+
+    @classmethod
+    def recording(cls, names, tensors, dtype):
+        """A recording tape over the named parameters for one autograd Function, attached to the current DDP sink."""
+        from .ddp import current_sink
+        tape = cls(dict(zip(names, tensors)), dtype, record=True)
+        tape.sink = current_sink()
+        if tape.sink is not None:
+            tape.sink.begin()
+        return tape
+
+    def finish(self, names):
+        """After backward(): the parameter gradients in ``names`` order (None where the sink assigned .grad itself)."""
+        if self.sink is None:
+            return [self.pgrad.get(n) for n in names]
+        self.sink.finish()
+        return self.sink.returned(names, [self.pgrad.get(n) for n in names])
 
     def prepack(self, plan):
         """Standardise + pack every conv weight of ``plan`` [(key, standardize, need_dgrad)] in one launch."""
@@ -134,116 +152,115 @@ class Tape:
             self.ops.append(bwd)
         return out
 
-    def gn_conv(self, x, key, k, stride, gn_key=None, G=0, residual=None, bias=False, out_f32=False,
-                standardize=None, pair=None):
-        """conv(relu(gn(x))) [+ residual] [+ bias] — Conv3d/conv3x3x3 :16-35 behind GN+ReLU :44-53."""
-        std = self.std if standardize is None else standardize
-        W = self.P[key + ".weight"]
-        cout, cin = W.shape[0], W.shape[1]
-        pf, pd, st = self.packed(key, std)
-        gn = None
-        if gn_key is not None:
-            gn = (self.stats(x, G), self.P[gn_key + ".weight"], self.P[gn_key + ".bias"], G)
-        b = self.P[key + ".bias"] if bias else None
-        res = residual.t if residual is not None else None
-        head = out_f32 and residual is None and ops.use_head(x.t.dtype, cin, cout, k, stride)
-        st16 = None
-        xn = None  # relu(gn(x)) stored by the forward ring: the weight gradient's operand (no GN prologue there)
+    def conv_fwd_form(self, x, pf, cout, k, stride, gn, res, b, out_f32, head):
+        """gn_conv's forward in the form that serves it: (output Act, xn). xn: relu(gn(x)) where the forward stored it,
+        the weight gradient's operand (no GN prologue there)."""
+        st16 = xn = None
         if head:  # precls_conv: streaming MFMA head (head.hip)
-            y = ops.head_fwd(x.t, pf, cout, b, gn)
-        elif self.record and b is None and not out_f32 and ops.ring_xn_ok(x.t, cout, k, stride, gn):
-            y, st16, xn = ops.conv_fwd_stats_xn(x.t, pf, cout, k, stride, gn, res)
-        elif b is None and not out_f32 and residual is None and ops.s2_normalise_once(x.t, cin, cout, k, stride, gn):
+            y = ops.head_fwd(x, pf, cout, b, gn)
+        elif b is not None or out_f32:  # (the plain conv only)
+            y = ops.conv_fwd(x, pf, cout, k, stride, gn, res, b, out_f32)
+        elif self.record and ops.ring_xn_ok(x, cout, k, stride, gn):
+            y, st16, xn = ops.conv_fwd_stats_xn(x, pf, cout, k, stride, gn, res)
+        elif res is None and ops.s2_normalise_once(x, x.shape[-1], cout, k, stride, gn):
             # stride-2 3^3 conv on the implicit GEMM: relu(gn(x)) materialised once (the GEMM's prologue normalised
             # every gathered element, 27/8 times per input element) and reused by the weight gradient
-            xn = ops.gn_apply(x.t, *gn)
+            xn = ops.gn_apply(x, *gn)
             y, st16 = ops.conv_fwd_stats(xn, pf, cout, k, stride, None)
-        elif gn is not None and b is None and not out_f32 and ops.epilogue_stats_cout(cout):
-            y, st16 = ops.conv_fwd_stats(x.t, pf, cout, k, stride, gn, res)
+        elif gn is not None and ops.epilogue_stats_cout(cout):
+            y, st16 = ops.conv_fwd_stats(x, pf, cout, k, stride, gn, res)
         else:
-            y = ops.conv_fwd(x.t, pf, cout, k, stride, gn, res, b, out_f32)
+            y = ops.conv_fwd(x, pf, cout, k, stride, gn, res)
         out = Act(y)
         if head and cout == 16:
             self.head_out = out  # the partial loss may hand its gradient to this head unformed (_TrunkFn)
         if st16 is not None:
             out.stats[16] = st16  # GroupNorm(16) statistics from the conv epilogue (consumed by the next GN)
+        return out, xn
+
+    def gn_conv(self, x, key, k, stride, gn_key=None, G=0, residual=None, bias=False, out_f32=False,
+                standardize=None, park=False):
+        """conv(relu(gn(x))) [+ residual] [+ bias] — Conv3d/conv3x3x3 :16-35 behind GN+ReLU :44-53. ``park``: this GN's
+        backward waits for the next conv's on the same x (block)."""
+        std = self.std if standardize is None else standardize
+        W = self.P[key + ".weight"]
+        cout, cin = W.shape[0], W.shape[1]
+        pf, pd, st = self.packed(key, std)
+        gn = (self.stats(x, G), self.P[gn_key + ".weight"], self.P[gn_key + ".bias"], G) if gn_key is not None else None
+        b = self.P[key + ".bias"] if bias else None
+        head = out_f32 and residual is None and ops.use_head(x.t.dtype, cin, cout, k, stride)
+        out, xn = self.conv_fwd_form(x.t, pf, cout, k, stride, gn, residual.t if residual is not None else None, b,
+                                     out_f32, head)
         if self.record:
+            def dgb():  # the GroupNorm's parameter-gradient destinations, for a launch that writes them itself
+                return self.grad_out(gn_key + ".weight", gn[1]), self.grad_out(gn_key + ".bias", gn[2])
+
             def bwd():
                 dy = out.grad
                 if dy is None:
-                    if pair == "finish" and x.gn_pend:  # the parked partner still owes its GN backward
-                        dA2, gn2, key2, s2c = x.gn_pend.pop()
-                        self.gn_bwd_one(x, ops.expand_s2(dA2, x.t.shape[:4]) if s2c else dA2, gn2, key2, G)
-                    return
-                parts = None  # GroupNorm-backward partials a data-gradient pass took (head or ring epilogue)
-                if head:  # dA, bf16 dy and the bias gradient in one pass over the fp32 dlogits
-                    db = self.grad_out(key + ".bias", b) if bias else None
-                    if isinstance(dy, DeferredLossGrad):  # the loss gradient formed inside the head's pass
-                        lg_, lab_, wt_, sums_, go_ = dy.payload
-                        assert lg_.data_ptr() == y.data_ptr() and lg_.shape == y.shape, "deferred loss gradient: not this head's logits"
-                        if gn is not None and pair is None and ops.head_gn_parts_ok(lg_, x.t, cin, gn):
-                            # the prologue GroupNorm's backward partials in the same pass (no partial pass over dA)
-                            dA, dyT, parts = ops.head_loss_bwd(lg_, lab_, wt_, sums_, go_, pd, cin, dbias=db,
-                                                               x0=x.t, gn=gn)
-                        else:
-                            dA, dyT = ops.head_loss_bwd(lg_, lab_, wt_, sums_, go_, pd, cin, dbias=db)
-                    else:
-                        dA, dyT = ops.head_bwd(dy, pd, cin, dbias=db)
-                    if bias:
-                        self.grad_done(key + ".bias")
-                else:
-                    if bias:
-                        ops.channel_sum(dy, out=self.grad_out(key + ".bias", b))
-                        self.grad_done(key + ".bias")
-                    if residual is not None:
-                        self.acc_grad(residual, dy)
-                    dyT = ops.cast(dy, self.dtype, pad_to=8)  # GEMM operand: channels padded to 8 (2-class head)
-                def dgb():  # the GroupNorm's parameter-gradient destinations, for a launch that writes them itself
-                    return self.grad_out(gn_key + ".weight", gn[1]), self.grad_out(gn_key + ".bias", gn[2])
-                paired = None  # weight gradient + data gradient (GN backward inside) in one launch: 12^3 / 6^3 levels
-                if xn is None and gn is not None and not head and pair is None:
-                    paired = ops.conv_bwd_pair_small(dyT, pd, x.t, k, stride, gn, dgb)
-                if paired is not None:
-                    part, ns, dA, parts = paired
-                elif xn is not None:
-                    part, ns = ops.conv_wgrad(dyT, xn, k, stride, None)
-                else:
-                    part, ns = ops.conv_wgrad(dyT, x.t, k, stride, gn)
-                if ops.EAGER_SLAB_SUM and ns >= ops.EAGER_SLAB_MIN:
-                    part, ns = ops.sum_slabs(part, ns, cout, cin)
-                self.pend_wgrad(part, ns, W, st, std, key + ".weight")
-                s2c = (gn is not None and pair == "park" and k == 1 and stride == 2
-                       and ops.s2_compact_dgrad_ok(dyT, cin, x.t.shape))
-                if paired is None and gn is not None and not head and pair != "park" \
-                        and not (pair == "finish" and x.gn_pend):
-                    fused = ops.conv_dgrad_gn(dyT, pd, cin, x.t, k, stride, gn, dgb)  # GN-bwd partials in the epilogue
-                    if fused is not None:
-                        dA, parts = fused
-                if parts is not None:
-                    pass
-                elif s2c:  # kept at the conv's output resolution: the paired GN backward reads it in place
-                    dA = ops.conv_dgrad_1x1s2_compact(dyT, pd, cin)
-                elif not head:
-                    dA = ops.conv_dgrad(dyT, pd, cin, x.t.shape[:4], k, stride)
-                if gn is not None and pair == "park":
-                    x.gn_pend = [(dA, gn, gn_key, s2c)]  # the block's gn1 backward (runs next) finishes the pair
-                elif gn is not None and pair == "finish" and x.gn_pend:
-                    dA2, gn2, key2, s2c2 = x.gn_pend.pop()
-                    dps = []
-                    for key_, g_ in ((gn_key, gn), (key2, gn2)):
-                        dps.append((self.grad_out(key_ + ".weight", g_[1]), self.grad_out(key_ + ".bias", g_[2])))
-                    x.grad = ops.gn_bwd2(dA, dA2, x.t, gn[0], (gn[1], gn[2]), (gn2[1], gn2[2]), G, dx=x.grad,
-                                         accumulate=x.grad is not None, dparams1=dps[0], dparams2=dps[1],
-                                         da2_s2=s2c2)
-                    for key_ in (gn_key, key2):
-                        self.grad_done(key_ + ".weight")
-                        self.grad_done(key_ + ".bias")
-                elif gn is not None:
-                    self.gn_bwd_one(x, dA, gn, gn_key, G, parts)
-                else:
-                    self.acc_grad(x, dA)
+                    return self.settle_parked(x, G)
+                alone = gn is not None and not park and not x.gn_pend  # this GN's backward runs by itself: fusable
+                dyT, dA, parts = self.output_side(dy, out.t, x.t, pd, gn if alone else None, key, b, residual, head)
+                r = ops.conv_bwd(dyT, pd, x.t, cout, k, stride, gn, dgb, xn, want_da=dA is None, fuse_gn=alone,
+                                 compact=park and gn is not None,
+                                 wgrad_done=partial(self.pend_wgrad, W=W, st=st, std=std, name=key + ".weight"))
+                dA, parts, compact = r if dA is None else (dA, parts, False)  # (the head's pass produced dA already)
+                self.prologue_bwd(x, dA, parts, gn, gn_key, G, park, compact)
             self.ops.append(bwd)
         return out
+
+    def settle_parked(self, x, G):
+        """No gradient reached a conv whose partner parked its GN backward on x: that one runs alone after all."""
+        if x.gn_pend:
+            dA2, gn2, key2, s2c = x.gn_pend.pop()
+            self.gn_bwd_one(x, ops.expand_s2(dA2, x.t.shape[:4]) if s2c else dA2, gn2, key2, G)
+
+    def output_side(self, dy, y, x, pd, gn, key, b, residual, head):
+        """Output side of a conv's backward -> (dyT, dA, parts): the bias gradient, the residual's share and dy as the
+        GEMM operand; on the streaming head one pass over the fp32 dlogits that also produces dA, and for ``gn`` (the
+        prologue GroupNorm, where its backward runs by itself) may take that backward's partials."""
+        if not head:
+            if b is not None:
+                ops.channel_sum(dy, out=self.grad_out(key + ".bias", b))
+                self.grad_done(key + ".bias")
+            if residual is not None:
+                self.acc_grad(residual, dy)
+            return ops.cast(dy, self.dtype, pad_to=8), None, None  # channels padded to 8 (2-class head)
+        cin = x.shape[-1]
+        db = self.grad_out(key + ".bias", b) if b is not None else None
+        parts = None
+        if not isinstance(dy, DeferredLossGrad):
+            dA, dyT = ops.head_bwd(dy, pd, cin, dbias=db)
+        else:  # the loss gradient formed inside the head's pass
+            lg, lab, wt, sums, go = dy.payload
+            assert lg.data_ptr() == y.data_ptr() and lg.shape == y.shape, "deferred loss gradient: not this head's logits"
+            if gn is not None and ops.head_gn_parts_ok(lg, x, cin, gn):  # (no partial pass over dA)
+                dA, dyT, parts = ops.head_loss_bwd(lg, lab, wt, sums, go, pd, cin, dbias=db, x0=x, gn=gn)
+            else:
+                dA, dyT = ops.head_loss_bwd(lg, lab, wt, sums, go, pd, cin, dbias=db)
+        if b is not None:
+            self.grad_done(key + ".bias")
+        return dyT, dA, parts
+
+    def prologue_bwd(self, x, dA, parts, gn, gn_key, G, park, compact):
+        """The backward of a conv's GN + ReLU prologue from dA. A block's gn1 and downsample GN read x with the same
+        statistics: the downsample's (``park``; ``compact``: its dA is at the conv's output resolution) waits on x for
+        gn1's, which runs next in the reversed tape and takes both in one pass."""
+        if gn is None:
+            self.acc_grad(x, dA)
+        elif park:
+            x.gn_pend = [(dA, gn, gn_key, compact)]
+        elif x.gn_pend:
+            dA2, gn2, key2, s2c2 = x.gn_pend.pop()
+            dps = [(self.grad_out(k_ + ".weight", g_[1]), self.grad_out(k_ + ".bias", g_[2]))
+                   for k_, g_ in ((gn_key, gn), (key2, gn2))]
+            x.grad = ops.gn_bwd2(dA, dA2, x.t, gn[0], (gn[1], gn[2]), (gn2[1], gn2[2]), G, dx=x.grad,
+                                 accumulate=x.grad is not None, dparams1=dps[0], dparams2=dps[1], da2_s2=s2c2)
+            for k_ in (gn_key, key2):
+                self.grad_done(k_ + ".weight")
+                self.grad_done(k_ + ".bias")
+        else:
+            self.gn_bwd_one(x, dA, gn, gn_key, G, parts)
 
     def gn_bwd_one(self, x, dA, gn, gn_key, G, parts=None):
         acc = dict(dx=x.grad, accumulate=x.grad is not None)
@@ -279,13 +296,10 @@ class Tape:
 
     def block(self, x, pre, stride, G):
         """NoBottleneck.forward, unet3D.py:56-73."""
-        # gn1 and the downsample GN read x with the same statistics: their backward runs as one fused pass (the
-        # downsample's backward runs first in the reversed tape and parks its dA, gn1's finishes the pair)
-        pair = pre + "downsample.2.weight" in self.P and ops.GN_BWD_PAIRS
-        h = self.gn_conv(x, pre + "conv1", 3, stride, gn_key=pre + "gn1", G=G, pair="finish" if pair else None)
-        if pre + "downsample.2.weight" in self.P:
+        h = self.gn_conv(x, pre + "conv1", 3, stride, gn_key=pre + "gn1", G=G)
+        if pre + "downsample.2.weight" in self.P:  # its GN backward runs paired with gn1's (prologue_bwd)
             r = self.gn_conv(x, pre + "downsample.2", 1, stride, gn_key=pre + "downsample.0", G=G,
-                             pair="park" if pair else None)
+                             park=ops.GN_BWD_PAIRS)
         else:
             r = x
         return self.gn_conv(h, pre + "conv2", 3, 1, gn_key=pre + "gn2", G=G, residual=r)
@@ -341,15 +355,15 @@ def compute_dtype(explicit=None):
     return torch.float32
 
 
+def ndhwc_grad(g, dtype=torch.float32):
+    """An NCDHW gradient from autograd as the tape reads it: contiguous NDHWC in ``dtype``."""
+    return g.permute(0, 2, 3, 4, 1).to(dtype).contiguous()
+
+
 class _TrunkFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cfg, dtype, names, x, *tensors):
-        from .ddp import current_sink
-        P = dict(zip(names, tensors))
-        tape = Tape(P, dtype, record=True)
-        tape.sink = current_sink()
-        if tape.sink is not None:
-            tape.sink.begin()
+        tape = Tape.recording(names, tensors, dtype)
         f, _ = tape.trunk(x, cfg)
         lg = tape.head(f, cfg)
         ctx.tape, ctx.out, ctx.names = tape, lg, names
@@ -368,15 +382,8 @@ class _TrunkFn(torch.autograd.Function):
         else:
             if isinstance(g, DeferredLossGrad):
                 g = g.materialize()
-            g = g.permute(0, 2, 3, 4, 1)
-            if not g.is_contiguous():
-                g = g.contiguous()
-            tape.backward(ctx.out, g.float())
-        if tape.sink is not None:
-            tape.sink.finish()
-        grads = [tape.pgrad.get(n) for n in ctx.names]
-        if tape.sink is not None:
-            grads = tape.sink.returned(ctx.names, grads)
+            tape.backward(ctx.out, ndhwc_grad(g))
+        grads = tape.finish(ctx.names)
         ctx.tape = ctx.out = None
         return (None, None, None, None, *grads)
 

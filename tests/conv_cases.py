@@ -6,7 +6,7 @@ no bound is zero where the reference is not).
 A row names the C entry point it launches (``entry``), the family of ops.ROUTES (or the weight-gradient family) that
 entry belongs to, the direction (fwd / dgrad / wgrad), and the conv: dt, n, cin -> cout (the FORWARD conv's channels,
 also for dgrad / wgrad), dims = the forward conv's INPUT extents, k, stride. ``routed``: True = production-routed
-(ops.conv_route / ops._wgrad_route with the default flags picks this family for this conv); False = forced (reached
+(ops.conv_route / ops.wgrad_route with the default flags picks this family for this conv); False = forced (reached
 through ``route=``, a module flag or a library option, restored afterwards). ``opts``: library options (csrc/common.h)
 set around the launch. ``slabs``: the split-K workspace handed to the launcher holds exactly this many slabs.
 

@@ -166,8 +166,8 @@ def _production_route(c):
     if c.dir == "wgrad":
         x = torch.empty((n, d, h, w, c.cin), dtype=c.dt, device="meta")
         dy = torch.empty((n,) + cc.out_dims(c) + (c.cout,), dtype=c.dt, device="meta")
-        r = ops._wgrad_route(dy, x, c.k, c.stride)
-        return {"ring": "wgrad_ring", True: "wgrad1" if c.k == 1 else "wgrad_brick", False: "wgrad_gemm"}[r]
+        r = ops.wgrad_route(dy, x, c.k, c.stride)
+        return {"ring": "wgrad_ring", "brick": "wgrad1" if c.k == 1 else "wgrad_brick", "gemm": "wgrad_gemm"}[r]
     el = 2 if c.dt == BF else 4
     if c.dir == "fwd":
         return ops.conv_route(c.dt, c.cin, c.cout, c.k, c.stride, shape, n * d * h * w * c.cin * el, False,

@@ -101,7 +101,7 @@ def test_bf16_conv_dgrad(gpu, conv_path, n, cin, cout, dims, s):
     assert err < 1e-2 * ref.abs().max().item(), err
 
 
-@pytest.mark.parametrize("brick", ["ring", True, False])
+@pytest.mark.parametrize("brick", ["ring", pytest.param("brick", id="True"), pytest.param("gemm", id="False")])
 @pytest.mark.parametrize("n,cin,cout,dims,s", SHAPES)
 def test_bf16_conv_wgrad(gpu, n, cin, cout, dims, s, brick):
     from u3d import ops
@@ -132,9 +132,9 @@ def test_wgrad_brick_s2_three_plane_bricks_match_two(gpu, n, cin, cout, dims):
     od = tuple(ops.out_dim(d, 3, 2) for d in dims)
     dy = torch.randn((n,) + od + (cout,), device=gpu).to(torch.bfloat16)
     with ops.option("WB_S2BD", 3):
-        part3, _ = ops.conv_wgrad(dy, x, 3, 2, (st, ga, be, G), brick=True)
+        part3, _ = ops.conv_wgrad(dy, x, 3, 2, (st, ga, be, G), brick="brick")
     with ops.option("WB_S2BD", 2):
-        part2, _ = ops.conv_wgrad(dy, x, 3, 2, (st, ga, be, G), brick=True)
+        part2, _ = ops.conv_wgrad(dy, x, 3, 2, (st, ga, be, G), brick="brick")
     a, b = part3.double().sum(0), part2.double().sum(0)
     scale = b.abs().max().item()
     assert (a - b).abs().max().item() <= 1e-5 * scale
@@ -156,9 +156,9 @@ def test_wgrad_brick_s2_two_co_tiles_matches_one(gpu, n, cin, cout, dims):
     x, w, st, ga, be, G = _case(gpu, n, cin, cout, dims, True, 7)
     od = tuple(ops.out_dim(d, 3, 2) for d in dims)
     dy = torch.randn((n,) + od + (cout,), device=gpu).to(torch.bfloat16)
-    part, _ = ops.conv_wgrad(dy, x, 3, 2, (st, ga, be, G), brick=True)
+    part, _ = ops.conv_wgrad(dy, x, 3, 2, (st, ga, be, G), brick="brick")
     with ops.option("WB_S2CO64", 0):
-        part1, _ = ops.conv_wgrad(dy, x, 3, 2, (st, ga, be, G), brick=True)
+        part1, _ = ops.conv_wgrad(dy, x, 3, 2, (st, ga, be, G), brick="brick")
     a, b = part.double().sum(0), part1.double().sum(0)
     assert (a - b).abs().max().item() <= 1e-5 * b.abs().max().item()
 

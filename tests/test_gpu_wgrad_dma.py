@@ -26,7 +26,7 @@ def test_wgrad_dma_ring_vs_brick_and_fp64(gpu, n, cin, cout, dims, use_gn):
     with ops.option("WR_TILE16", 1):
         p_dma, _ = ops.conv_wgrad(dy, x, 3, 1, gn, brick="ring")
         p_dma2, _ = ops.conv_wgrad(dy, x, 3, 1, gn, brick="ring")
-    p_brk, _ = ops.conv_wgrad(dy, x, 3, 1, gn, brick=True)
+    p_brk, _ = ops.conv_wgrad(dy, x, 3, 1, gn, brick="brick")
     torch.cuda.synchronize()
     assert torch.equal(p_dma, p_dma2), "DMA ring not deterministic"
     dw = p_dma.sum(0).double()[:, :cout, :cin]

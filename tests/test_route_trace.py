@@ -2,7 +2,9 @@
 conv wrapper of u3d.ops on meta tensors (library calls recorded with their scalar arguments, workspace requests with
 slot and size, nothing launched) and route_trace_expected.json holds a digest of each trace. The digests were written
 by ``tools/route_trace.py --write`` from the tree before the routing was gathered into ops.conv_route, so a routing
-change shows here as a changed digest (``--dump DIR`` on both trees, then diff, names the call)."""
+change shows here as a changed digest (``--dump DIR`` on both trees, then diff, names the call). The configurations
+that steer a conv's backward on the tape (backward flags, tape pieces, a formed loss gradient) were added with
+ops.conv_bwd; their digests were written from the u3d package of the commit before it."""
 import json
 import os
 import sys

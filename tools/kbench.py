@@ -83,7 +83,7 @@ def _dgrad_gn(n, c, s):
 
 def _wgrad(n, cin, cout, s, k, stride):
     x, pf, pd, g, r, dy, flop = conv_case(n, cin, cout, s, k, stride, True)
-    us = t_(lambda: ops.conv_wgrad(dy, x, k, stride, g, brick={"ring": "ring", "brick": True}.get(os.environ.get("KB_WGRAD", ""))))
+    us = t_(lambda: ops.conv_wgrad(dy, x, k, stride, g, brick={"ring": "ring", "brick": "brick"}.get(os.environ.get("KB_WGRAD", ""))))
     return us, flop
 
 

@@ -87,6 +87,22 @@ FLAG_SETS = {
     "small_fuse_off": dict(SMALL_FUSE=False),
     "conv32_brick": dict(CONV32_FN="u3d_conv32_brick"),
     "convg_persist_off": dict(CONVG_PERSIST=0),
+    # the flags that steer the backward forms of a conv on the tape (ops.conv_bwd, Tape.gn_conv)
+    "gn_pairs_off": dict(GN_BWD_PAIRS=False),
+    "small_pair_off": dict(SMALL_BWD_PAIR=False),
+    "s2_compact_off": dict(S2_COMPACT=False),
+    "s2_norm_once_off": dict(S2_NORM_ONCE=False),
+    "gn_bwd_fused_off": dict(GN_BWD_FUSED=False),
+    "gn_bwd_fused_brick_off": dict(GN_BWD_FUSED_BRICK=False),
+    "small_gb_off": dict(SMALL_GB=False),
+    "head_gn_parts_off": dict(HEAD_GN_PARTS=False),
+    "head_dbias_off": dict(HEAD_DBIAS_FUSED=False),
+    "eager_slab_sum": dict(EAGER_SLAB_SUM=True),
+    "wgrad_queue": dict(WGRAD_QUEUE=True),
+    "ring_wgrad_off": dict(USE_RING_WGRAD=False),
+    "brick_wgrad_off": dict(USE_BRICK_WGRAD=False),
+    "collective_fused_finalize": dict(COLLECTIVE_IN_FLIGHT=[True], FUSED_FINALIZE=True),  # (the tolerant DDP step)
+    "collective_small_pair_off": dict(COLLECTIVE_IN_FLIGHT=[True], SMALL_BWD_PAIR=False),
 }
 
 
@@ -105,8 +121,9 @@ def _model(name):
         return unet3D.unet3D_g([1, 2, 2, 2, 2], num_classes=3, weight_std=True)
 
 
-def trunk_step(model, shape, dtype, record=True):
-    """Tape.trunk + Tape.head (+ Tape.backward) of ``model`` on a meta input [n, d, h, w]."""
+def trunk_step(model, shape, dtype, record=True, plain_grad=False):
+    """Tape.trunk + Tape.head (+ Tape.backward) of ``model`` on a meta input [n, d, h, w]. ``plain_grad``: the loss
+    gradient reaches the head formed (an fp32 tensor), as from any loss but the partial-label one."""
     m = _model(model)
     n, d, h, w = shape
     cin = m.conv0.weight.shape[1] if hasattr(m, "conv0") else m.conv1.weight.shape[1]
@@ -116,7 +133,7 @@ def trunk_step(model, shape, dtype, record=True):
     if not record:
         return
     y = lg.t
-    if getattr(tape, "head_out", None) is lg:  # the loss gradient handed to the streaming head unformed
+    if getattr(tape, "head_out", None) is lg and not plain_grad:  # the loss gradient handed to the streaming head unformed
         payload = (y, meta(y.shape[:-1]), meta((y.shape[-1],)), meta((y.shape[-1], 4), torch.float64), meta((1,)))
         g = DeferredLossGrad((y.shape, y.stride(), y.dtype, y.device), None, payload, None)
     else:
@@ -132,6 +149,63 @@ TRUNK_INPUTS = {
     "fp32_1x32": ((1, 32, 32, 32), torch.float32),
 }
 MODELS = ("unet3D", "baseline", "unet3D_g")
+
+
+# ------------------------------------------------------------------------------------------ tape pieces
+def _conv_params(P, key, cin, cout, k, gn_key=None, bias=False):
+    P[key + ".weight"] = meta((cout, cin, k, k, k))
+    if bias:
+        P[key + ".bias"] = meta((cout,))
+    if gn_key is not None:
+        P[gn_key + ".weight"], P[gn_key + ".bias"] = meta((cin,)), meta((cin,))
+
+
+def tape_piece(build, cin, edge, gdtype=torch.bfloat16, n=2):
+    """One piece of the tape, forward and backward, on a meta Act [n, edge^3, cin]: build(P) fills the parameters and
+    returns the function (tape, act) -> output Act; the gradient handed in has ``gdtype``."""
+    P = {}
+    fwd = build(P)
+    tape = trunk.Tape(P, torch.bfloat16, record=True)
+    out = fwd(tape, trunk.Act(meta((n, edge, edge, edge, cin), torch.bfloat16)))
+    tape.backward(out, meta(out.t.shape, gdtype))
+
+
+def _block(cin, cout, stride, down):
+    def build(P):
+        _conv_params(P, "b.conv1", cin, cout, 3, "b.gn1")
+        _conv_params(P, "b.conv2", cout, cout, 3, "b.gn2")
+        if down:
+            _conv_params(P, "b.downsample.2", cin, cout, 1, "b.downsample.0")
+        return lambda tape, x: tape.block(x, "b.", stride, 16)
+    return build
+
+
+def _lone_conv(c):  # no GroupNorm in front: unet3D.Conv3d on its own (subgraph), the conv0 model's conv1
+    def build(P):
+        _conv_params(P, "c", c, c, 3)
+        return lambda tape, x: tape.gn_conv(x, "c", 3, 1)
+    return build
+
+
+def _deep_head(cin):  # feam._feam3_forward's deepout heads; cin 32 / 64 run the streaming head, 128 the implicit GEMM
+    def build(P):
+        _conv_params(P, "deepout.2", cin, 16, 1, "deepout.0", bias=True)
+        return lambda tape, x: tape.gn_conv(x, "deepout.2", 1, 1, gn_key="deepout.0", G=16, bias=True, out_f32=True,
+                                            standardize=False)
+    return build
+
+
+TAPE_EDGES = (12, 48)  # 2 x 12^3: the small family; 2 x 48^3: the ring (32 -> 32) and the brick
+TAPE_PIECES = {
+    "block_down_s2": (_block(32, 64, 2, True), 32, torch.bfloat16),
+    "block_down_s1": (_block(64, 32, 1, True), 64, torch.bfloat16),
+    "block_32": (_block(32, 32, 1, False), 32, torch.bfloat16),
+    "block_64": (_block(64, 64, 1, False), 64, torch.bfloat16),
+    "conv_no_gn_32": (_lone_conv(32), 32, torch.bfloat16),
+    "conv_no_gn_64": (_lone_conv(64), 64, torch.bfloat16),
+    "deep_head_32": (_deep_head(32), 32, torch.float32),
+    "deep_head_128": (_deep_head(128), 128, torch.float32),
+}
 
 
 # ------------------------------------------------------------------------------------------ single wrappers
@@ -220,6 +294,11 @@ def configs():
                     trunk_step(m, (2, 96, 96, 96), torch.bfloat16)
             out[f"trunk/{m}/bf16_2x96/{fname}"] = run
         out[f"trunk/{m}/bf16_2x96/inference"] = lambda t, m=m: trunk_step(m, (2, 96, 96, 96), torch.bfloat16, False)
+    out["trunk/baseline/bf16_2x96/plain_grad"] = lambda t: trunk_step("baseline", (2, 96, 96, 96), torch.bfloat16,
+                                                                      plain_grad=True)
+    for pname, (build, cin, gdtype) in TAPE_PIECES.items():
+        for e in TAPE_EDGES:
+            out[f"tape/{pname}/{e}"] = lambda t, b=build, c=cin, e=e, g=gdtype: tape_piece(b, c, e, g)
     for cin, cout in CHANNELS:
         for k, stride in KS:
             out[f"direct/{cin}-{cout}/k{k}s{stride}"] = \
