@@ -659,6 +659,36 @@ int u3d_aug_affine(float* x, long long V, float mul, float add, u3d_stream_t str
 int u3d_aug_contrast(float* x, long long V, float factor, const float* stats, int preserve_range,
                      u3d_stream_t stream);
 
+/* ---------------------------------------------------------------- atlas prior (csrc/atlas.hip)
+ * u3d_atlas_crop: the dataset's nearest resize of the atlas [C][Ah][Aw][Ad] to the image shape (Ih, Iw, Id)
+ * (MOTSDataset.py:357), pad_image2 (:372), crop (:383) and transpose (:392) in one pass that forms only the crop:
+ * out[c][dd][hh][ww] = inside ? atlas[c][(y Ah) / Ih][(x Aw) / Iw][(z Ad) / Id] : 0, y = b0 + hh, x = c0 + ww,
+ * z = a0 + dd, inside = y < Ih && x < Iw && z < Id; offsets and crop as u3d_crop_transpose, out [C][cd][ch][cw]. The
+ * source index is the exact integer floor(i in / out), what F.interpolate gives on the float64 atlas the reference
+ * feeds (not the float32 floorf(i * (float)in / out) of a float32 or device interpolate). */
+int u3d_atlas_crop(const float* atlas, int C, int Ah, int Aw, int Ad, int Ih, int Iw, int Id, int b0, int c0, int a0,
+                   int ch, int cw, int cd, float* out, u3d_stream_t stream);
+/* Refiner / discriminator inputs of train_amos_atlas_final.py:277-365 for one sample: out[k][0][v] =
+ * softmax_c(logits[.][v])[first + index[k]] and, when atlas is given, out[k][1][v] = atlas[index[k]][v] (atlas
+ * [natlas][V] contiguous; otherwise out has one channel). logits by element strides (class lsc, voxel lsv): NCDHW and
+ * the native head's NDHWC storage are both read in place. index: K host ints (read during the call), duplicates
+ * allowed; C <= 32, 1 <= K <= 64, first 0 or 1; out [K][1|2][V] contiguous.
+ * Backward from grad_out = d out [K][nch][V] (channel 0 is read): dlogits_c = p_c (G_c - sum_j p_j G_j) with G_c the
+ * sum of grad_out[k][0] over the k with first + index[k] == c (ascending k), p recomputed, written with the logits'
+ * strides (every class of every voxel). The atlas gets no gradient. */
+int u3d_select_probs_fwd(const float* logits, long long lsc, long long lsv, int C, long long V, int first,
+                         const int* index, int K, const float* atlas /* nullable */, int natlas, float* out,
+                         u3d_stream_t stream);
+int u3d_select_probs_bwd(const float* logits, long long lsc, long long lsv, int C, long long V, int first,
+                         const int* index, int K, const float* grad_out, int nch, float* dlogits, u3d_stream_t stream);
+/* get_dice / get_dice2 with an atlas (evaluate_amos.py:144-151, :172-179): per sample s and organ l < num_class the
+ * gated prediction (softmax(logits)[l+1] + 0.15f) > (1 - atlas[s][l]) against labels == l+1. logits NDHWC [S][V][C],
+ * labels [S][V], atlas [S][natlas][V] (natlas >= num_class, num_class <= C - 1); counts, metrics as u3d_dice_metric;
+ * argmax [S][V] (nullable) is the plain argmax(softmax), as the reference returns it in this branch too. */
+int u3d_dice_metric_atlas(const float* logits, const float* labels, const float* atlas, int natlas, int S, long long V,
+                          int C, int num_class, long long* counts, float* metrics, long long* argmax,
+                          u3d_stream_t stream);
+
 /* ---------------------------------------------------------------- style discriminators (csrc/disc.hip)
  * get_style_discriminator_output (unet3D.py:1832-1849), deep_style_discriminator_output (:1852-1905),
  * norm_style_discriminator_output (:1907-1947), as train_amos_atlas_final.py:320-379 drives them.

@@ -321,6 +321,11 @@ __device__ __forceinline__ void gn_bwd_coefs(const double* cs, int n, int c, int
 // wave per (sample, group), fixed-order fp64 combine (conv_ring.hip). m = values per group and sample.
 int launch_gn16_finalize(const float* spart, int n, int wps, double m, float* stats, hipStream_t s);
 
+// Dice / sensitivity / precision of the hard Dice metrics from their integer counts cnt[S][ncls][3] = (TP, P, T), as
+// dice_score / senc_score / spec_score form them, averaged over the S samples: m[ncls][3] (dice_final_kernel, loss.hip;
+// shared with the atlas-gated metric of atlas.hip).
+int launch_dice_final(const unsigned long long* cnt, int S, int ncls, float* m, hipStream_t s);
+
 // 16-byte vector of T: 8 bf16 or 4 f32.
 template <typename T> struct Vec16 { static constexpr int N = 16 / sizeof(T); };
 

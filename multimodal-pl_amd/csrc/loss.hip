@@ -486,6 +486,11 @@ static int loss_blocks(long long nvox) {
   return (int)std::min<long long>(U3D_LOSS_NB, std::max<long long>(1, (nvox + LT - 1) / LT));
 }
 
+int launch_dice_final(const unsigned long long* cnt, int S, int ncls, float* m, hipStream_t s) {
+  hipLaunchKernelGGL(dice_final_kernel, dim3(1), dim3(64), 0, s, cnt, S, ncls, m);
+  return 0;
+}
+
 }  // namespace u3d
 
 using namespace u3d;

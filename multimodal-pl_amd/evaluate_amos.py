@@ -1,8 +1,10 @@
 """Drop-in for the metric part of the reference evaluate_amos.py.
 
-get_dice (evaluate_amos.py:128-154, atlas=None branch) runs as one fused HIP pass: per-voxel argmax of the
+get_dice (evaluate_amos.py:128-154) runs as one fused HIP pass: per-voxel argmax of the
 softmax, integer per-class counts, and the fp32 dice / sensitivity / precision averaged over samples exactly
-as the reference's dice_score / senc_score / spec_score (:92-126) compute them from the counts.
+as the reference's dice_score / senc_score / spec_score (:92-126) compute them from the counts. Its atlas branch
+(:144-151, the same lines in get_dice2 :172-179) counts the atlas-gated prediction
+(softmax + 0.15) > (1 - atlas) per organ in one pass of its own (u3d_dice_metric_atlas).
 dice_score / spec_score / senc_score themselves are kept as the reference's small tensor helpers.
 Sliding-window inference (predict_sliding, _get_gaussian, :184-279) keeps the
 reference's tiling, multi-net averaging and flip test-time augmentation, but accumulates on the device
@@ -43,10 +45,40 @@ def senc_score(preds, labels):
     return (num / (torch.sum(target, dim=1) + 1)).mean()
 
 
+def _dice_atlas(preds, labels, atlas, num_class):
+    """The atlas branch of get_dice / get_dice2 (the same lines in both, evaluate_amos.py:144-151, :172-179): one
+    fused pass (u3d_dice_metric_atlas). Returns (metrics [num_class, 3], argmax [S, D, H, W])."""
+    from u3d._lib import call
+    ops.require_device(preds, labels, atlas)
+    S, C = preds.shape[0], preds.shape[1]
+    if num_class > C - 1:  # preds_r[:, l + 1] at l + 1 == C
+        raise IndexError(f"index {C} is out of bounds for dimension 1 with size {C}")
+    if atlas.shape[1] < num_class:  # atlas[:, l]
+        raise IndexError(f"index {atlas.shape[1]} is out of bounds for dimension 1 with size {atlas.shape[1]}")
+    lg = ndhwc_view(preds.float())
+    V = lg.numel() // (S * C)
+    lab = labels.float().reshape(S, -1).contiguous()
+    at = atlas.float().reshape(atlas.shape[0], atlas.shape[1], -1).contiguous()
+    if lab.shape[1] != V or at.shape[0] != S or at.shape[2] != V:
+        raise RuntimeError(f"get_dice: labels {tuple(labels.shape)} / atlas {tuple(atlas.shape)} vs predictions "
+                           f"{tuple(preds.shape)}")
+    counts = torch.empty((S, num_class, 3), dtype=torch.int64, device=lg.device)
+    metrics = torch.empty((num_class, 3), dtype=torch.float32, device=lg.device)
+    am = torch.empty(lg.shape[:-1], dtype=torch.int64, device=lg.device)
+    call("u3d_dice_metric_atlas", lg.data_ptr(), lab.data_ptr(), at.data_ptr(), at.shape[1], S, V, C, num_class,
+         counts.data_ptr(), metrics.data_ptr(), am.data_ptr(), ops._stream())
+    return metrics, am
+
+
 def get_dice(preds, labels, t_id, atlas=None, num_class=13):
-    """Returns (dices, senc, spec, argmax) like the reference: three lists of 0-dim tensors + the argmax map."""
+    """Returns (dices, senc, spec, argmax) like the reference: three lists of 0-dim tensors + the argmax map.
+    With ``atlas`` [S, >= num_class, D, H, W] (fp32; float64 is cast) each organ's prediction is the reference's
+    atlas-gated one, (softmax(preds)[:, l + 1] + 0.15) > (1 - atlas[:, l]) (evaluate_amos.py:144-151), scored by one
+    fused pass (u3d_dice_metric_atlas); the fourth value stays the plain argmax map. CPU tensors raise U3DError."""
     if atlas is not None:
-        raise NotImplementedError("get_dice atlas branch (evaluate_amos.py:144-151) is not on the native path")
+        metrics, am = _dice_atlas(preds, labels, atlas, num_class)
+        return ([metrics[l, 0] for l in range(num_class)], [metrics[l, 1] for l in range(num_class)],
+                [metrics[l, 2] for l in range(num_class)], am)
     ops.require_device(preds, labels)
     lg = ndhwc_view(preds.float())
     lab = labels.float().reshape(preds.shape[0], -1).contiguous()
@@ -60,9 +92,13 @@ def get_dice(preds, labels, t_id, atlas=None, num_class=13):
 def get_dice2(preds, labels, t_id, atlas=None, num_class=13):
     """Reference evaluate_amos.py:156-182 (the refiner's metric, train_amos_atlas_final.py:294): preds = the
     refiner output [num_class organs, 2, D, H, W]; organ l's binary prediction argmax(softmax(preds[l])) == 1 is
-    scored against labels == l+1. One fused pass (u3d_dice_metric_binary). Returns (dices, senc, spec, argmax)."""
+    scored against labels == l+1. One fused pass (u3d_dice_metric_binary). Returns (dices, senc, spec, argmax).
+    With ``atlas`` the reference runs get_dice's atlas lines unchanged (:172-179: preds_r[:, l+1] over the class
+    dim, every sample of the batch scored against labels == l+1), so this routes to the same kernel
+    (u3d_dice_metric_atlas); on the refiner's 2-channel layout preds_r[:, l+1] is out of range at l = 1 and the
+    reference's IndexError is raised here too."""
     if atlas is not None:
-        raise NotImplementedError("get_dice2 atlas branch (evaluate_amos.py:170-180) is not on the native path")
+        return get_dice(preds, labels, t_id, atlas=atlas, num_class=num_class)
     from u3d._lib import call
     from u3d.loss import _voxel_strides
     ops.require_device(preds, labels)

@@ -143,6 +143,10 @@ _SIGS = {
     "u3d_aug_blur_axis": [P, P, L, I, L, P, I, P],
     "u3d_aug_affine": [P, L, F, F, P],
     "u3d_aug_contrast": [P, L, F, P, I, P],
+    "u3d_atlas_crop": [P, I, I, I, I, I, I, I, I, I, I, I, I, I, P, P],
+    "u3d_select_probs_fwd": [P, L, L, I, L, I, P, I, P, I, P, P],
+    "u3d_select_probs_bwd": [P, L, L, I, L, I, P, I, P, I, P, P],
+    "u3d_dice_metric_atlas": [P, P, P, I, I, L, I, I, P, P, P, P],
     "u3d_disc_conv_fwd_splits": [I, I, I, I, I, I],
     "u3d_disc_conv_fwd_ws_bytes": [I, I, I, I, I, I],
     "u3d_disc_conv_fwd": [I, P, I, I, I, I, I, I, I, P, P, P, I, I, I, I, P, P],

@@ -4,6 +4,9 @@
   truncate (:171-186: CT clipped to [-325, 325] / 325 for case ids < 500, MRI z-scored over the padded volume),
   the random crop (offsets drawn with np.random in the reference's order b, c, a) and the (H, W, D) -> (D, H, W)
   transpose — one device pass per tensor (u3d_crop_transpose; the MRI statistics by u3d_volume_stats).
+* ``atlas_crop``: the atlas side of the same lines starting from the raw atlas: the nearest resize to the image's shape
+  (:357) is taken inside the crop (u3d_atlas_crop), so the image-sized atlas (13 x H x W x D floats) is never formed.
+  ``crop_patch(..., atlas=raw)`` uses it.
 * ``train_transform``: my_collate's batchgenerators transforms (get_train_transform, :33-52) with their published
   parameters: Gaussian noise (p 0.1), Gaussian blur (sigma U(0.5, 1), per channel p 0.5, p 0.2), multiplicative
   brightness U(0.75, 1.25) (p 0.15), additive brightness N(0, 0.1) (per channel p 0.5, p 0.15), contrast
@@ -47,9 +50,33 @@ def crop_transpose(src, offsets, crop, mode=MODE_COPY, stats=None):
     return out
 
 
-def crop_patch(image, label, catlas, name, crop_size, usage="train", rng=np.random):
+def atlas_crop(atlas, image_shape, offsets, crop):
+    """The dataset's atlas path without the image-sized intermediate: atlas [C, Ah, Aw, Ad] device (fp32; a float64
+    tensor is cast once, the rounding of the driver's later .float()), image_shape (H, W, D) as the dataset sees the
+    image before pad_image, offsets (b, c, a) and crop (ch, cw, cd) as crop_transpose -> [C, cd, ch, cw], equal to
+    crop_transpose(F.interpolate(atlas[None], image_shape)[0], offsets, crop) with the nearest resize taken as the
+    reference takes it, on a float64 CPU tensor: source index floor(i * in / out) in integers (u3d_atlas_crop). A
+    float32 or device interpolate rounds i * (in / out) in float32 and lands one voxel off at some sizes."""
+    ops.require_device(atlas)
+    if atlas.dim() != 4 or len(image_shape) != 3:
+        raise ValueError(f"atlas_crop: atlas {tuple(atlas.shape)} must be [C, Ah, Aw, Ad], image_shape (H, W, D)")
+    a = atlas.float().contiguous()
+    C, Ah, Aw, Ad = a.shape
+    ch, cw, cd = (int(v) for v in crop)
+    out = torch.empty((C, cd, ch, cw), dtype=torch.float32, device=a.device)
+    call("u3d_atlas_crop", a.data_ptr(), C, Ah, Aw, Ad, int(image_shape[0]), int(image_shape[1]), int(image_shape[2]),
+         int(offsets[0]), int(offsets[1]), int(offsets[2]), ch, cw, cd, out.data_ptr(), ops._stream())
+    return out
+
+
+def crop_patch(image, label, catlas, name, crop_size, usage="train", rng=np.random, atlas=None):
     """image / label [H, W, D], catlas [13, H, W, D] device tensors as read (sitk arrays); crop_size = (d, h, w) as
-    the dataset's (crop_d, crop_h, crop_w). Returns image [1, D, H, W], label [1, D, H, W], catlas [13, D, H, W]."""
+    the dataset's (crop_d, crop_h, crop_w). Returns image [1, D, H, W], label [1, D, H, W], catlas [13, D, H, W].
+    ``atlas=``: the raw atlas [13, Ah, Aw, Ad] (device, fp32 or float64) in place of catlas (which must then be None;
+    both is a ValueError): the resize of MOTSDataset.py:357 happens inside the crop (atlas_crop), the draws and the
+    three outputs are those of the call with catlas = the reference's resized atlas."""
+    if atlas is not None and catlas is not None:
+        raise ValueError("crop_patch: pass catlas (already at image size) or atlas= (raw, resized in the crop), not both")
     cd, ch, cw = crop_size
     H, W, D = image.shape
     ph, pw, pd = max(H, ch + 5), max(W, cw + 5), max(D, cd + 5)   # pad_image to crop + 5 (zeros)
@@ -67,7 +94,10 @@ def crop_patch(image, label, catlas, name, crop_size, usage="train", rng=np.rand
         out_hw = (ph, pw, pd)
     img = crop_transpose(image, (b, c, a), out_hw, MODE_MRI if mri else MODE_CT, stats)
     lab = crop_transpose(label, (b, c, a), out_hw)
-    cat = crop_transpose(catlas, (b, c, a), out_hw) if catlas is not None else None
+    if atlas is not None:
+        cat = atlas_crop(atlas, (H, W, D), (b, c, a), out_hw)
+    else:
+        cat = crop_transpose(catlas, (b, c, a), out_hw) if catlas is not None else None
     return img, lab, cat
 
 

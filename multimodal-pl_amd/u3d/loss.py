@@ -261,6 +261,80 @@ def consistency_aux(logits, attns, refine, label_t, weight_feature, confi=0.10):
     return _ConsistFn.apply(logits, refine, label_t, weight_feature, confi, *attns)
 
 
+# ------------------------------------------- refiner / discriminator inputs (train_amos_atlas_final.py:277-365)
+SELECT_CMAX, SELECT_KMAX = 32, 64   # csrc/atlas.hip: classes, selected organs
+
+
+class _SelectProbsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, atlas, index, first):
+        lg, (_, lsc, lsv) = _voxel_strides(logits.float(), 2)
+        C = lg.shape[1]
+        D, H, W = lg.shape[2:]
+        V = D * H * W
+        K, nch = len(index), 1 if atlas is None else 2
+        idx = (ctypes.c_int * K)(*index)
+        out = torch.empty((K, nch, D, H, W), dtype=torch.float32, device=lg.device)
+        ops.call("u3d_select_probs_fwd", lg.data_ptr(), lsc, lsv, C, V, first, idx, K,
+                 atlas.data_ptr() if atlas is not None else None, atlas.shape[0] if atlas is not None else 0,
+                 out.data_ptr(), ops._stream())
+        ctx.save_for_backward(lg)
+        ctx.geo = (lsc, lsv, C, V, first, tuple(index), nch)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (lg,) = ctx.saved_tensors
+        lsc, lsv, C, V, first, index, nch = ctx.geo
+        K = len(index)
+        idx = (ctypes.c_int * K)(*index)
+        go = g.float().contiguous()
+        # the logits' own shape and strides (NCDHW, or an NCDHW view of NDHWC storage): autograd sums it with the loss
+        # gradient of the same logits without a layout copy
+        dl = torch.empty_strided(lg.shape, lg.stride(), dtype=torch.float32, device=lg.device)
+        ops.call("u3d_select_probs_bwd", lg.data_ptr(), lsc, lsv, C, V, first, idx, K, go.data_ptr(), nch,
+                 dl.data_ptr(), ops._stream())
+        return dl, None, None, None
+
+
+def select_probs(logits, index, atlas=None, first=0):
+    """out[k, 0] = softmax(logits, 1)[0, first + index[k]] and, with an atlas [A, D, H, W], out[k, 1] = atlas[index[k]]:
+    [K, 1 | 2, D, H, W] fp32, one pass (u3d_select_probs_fwd), with the gradient of channel 0 back to the logits
+    (u3d_select_probs_bwd; the atlas gets none). logits [1, C, D, H, W], NCDHW or the native head's NCDHW view of
+    NDHWC storage, read in place. index: ints (list, tuple, tensor), duplicates allowed, negative values count from
+    the end as in tensor[index]; an empty index returns an empty tensor without a launch."""
+    ops.require_device(logits, *([atlas] if atlas is not None else []))
+    if logits.dim() != 5 or logits.shape[0] != 1:
+        raise ValueError(f"select_probs: logits {tuple(logits.shape)} must be one sample [1, C, D, H, W]")
+    C, sp = logits.shape[1], tuple(logits.shape[2:])
+    if torch.is_tensor(index):
+        if index.dtype == torch.bool:
+            index = index.nonzero().reshape(-1)
+        index = index.reshape(-1).tolist()
+    n = C - first
+    if atlas is not None:
+        if atlas.dim() != 4 or tuple(atlas.shape[1:]) != sp:
+            raise RuntimeError(f"select_probs: atlas {tuple(atlas.shape)} vs the logits' volume {sp} (torch.cat needs "
+                               "equal sizes)")
+        if atlas.shape[0] != n:
+            raise RuntimeError(f"select_probs: {n} organ maps and {atlas.shape[0]} atlas channels (torch.cat needs "
+                               "equal sizes)")
+        atlas = atlas.detach().float().contiguous()
+    idx = []
+    for i in index:
+        i = int(i)
+        if not -n <= i < n:
+            raise IndexError(f"index {i} is out of bounds for dimension 0 with size {n}")
+        idx.append(i % n)
+    if C > SELECT_CMAX or len(idx) > SELECT_KMAX or first not in (0, 1):
+        from ._lib import U3DError
+        raise U3DError(f"select_probs: C = {C} (at most {SELECT_CMAX}), {len(idx)} selected (at most {SELECT_KMAX}), "
+                       f"first = {first} (0 or 1)")
+    if not idx:
+        return torch.empty((0, 1 if atlas is None else 2) + sp, dtype=torch.float32, device=logits.device)
+    return _SelectProbsFn.apply(logits, atlas, tuple(idx), int(first))
+
+
 class _Full2Fn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, t, m, sigmoid, uce):

@@ -1,5 +1,7 @@
 """Drop-in for the train-step helpers of the reference utils.py (lr_poly :53-54, adjust_learning_rate :56-60,
-extant_file :62-70, all_reduce_tensor :72-74, seedfix :116-149, get_logger :43-51)."""
+extant_file :62-70, all_reduce_tensor :72-74, seedfix :116-149, get_logger :43-51), and native forms of the
+driver's own lines that build the refiner / discriminator inputs from the class logits and the atlas prior
+(organ_atlas_pairs, attention_pairs: train_amos_atlas_final.py:277-365)."""
 import argparse
 import os
 
@@ -64,6 +66,33 @@ def mask_aug(mask, aug_times=2):
         for j in range(aug_times):
             out[i * aug_times + j] = mask[i]
     return out
+
+
+def organ_atlas_pairs(preds, catlas, index):
+    """Native form of the driver's refiner / discriminator input (train_amos_atlas_final.py:277+287, :290, :337, :345,
+    :355, :365), which the driver may adopt as it may losses.make_partial_target:
+
+        torch.cat([torch.softmax(preds, 1)[0, 1:].unsqueeze(1), catlas.unsqueeze(1)], 1)[index].float()
+
+    preds [1, C, D, H, W] class logits (device; NCDHW or the native head's layout, read in place), catlas
+    [C - 1, D, H, W] the atlas prior, index the organs (tlist / flist / clist: ints, duplicates allowed) ->
+    [len(index), 2, D, H, W] fp32: channel 0 the organ's probability (fp32 softmax), channel 1 its atlas map (a copy,
+    bit for bit). One pass (u3d_select_probs_fwd): one softmax per voxel, only the selected organs written. A gradient
+    flows back to preds (u3d_select_probs_bwd), none to the atlas; pass preds.detach() where the driver detaches.
+    No fallback: CPU tensors raise U3DError."""
+    from u3d.loss import select_probs
+    return select_probs(preds, index, atlas=catlas, first=1)
+
+
+def attention_pairs(attn, index):
+    """The f_m entries of the driver's discriminator calls (train_amos_atlas_final.py:337, :355):
+
+        torch.softmax(attn, 1)[0][index].unsqueeze(1)
+
+    attn [1, organs, d, h, w] attention logits -> [len(index), 1, d, h, w] fp32, with the gradient back to attn
+    (u3d_select_probs_fwd/_bwd); pass attn.detach() where the driver detaches."""
+    from u3d.loss import select_probs
+    return select_probs(attn, index, atlas=None, first=0)
 
 
 def seedfix(seed):

@@ -34,15 +34,14 @@ def step(deep_up, organs, patch, device, weight_gan=0.01):
     label_t = (torch.rand(organs, generator=g) > 0.5).long()
     flist = [i for i in range(organs) if label_t[i] == 0][: max(1, organs // 2)]
     clist = list(range(organs))
-    probs = torch.softmax(logits, dim=1)[0, 1:]                       # [organs, D, H, W]
+    from utils import attention_pairs, organ_atlas_pairs
 
     def call(idx, detach):
-        organ = probs.detach() if detach else probs
-        x_in = torch.stack([organ, catlas], dim=1)[idx].float()       # [len(idx), 2, D, H, W]
+        # [len(idx), 2, D, H, W]: the organs' probabilities and atlas maps (driver :337 / :345 / :355 / :365)
+        x_in = organ_atlas_pairs(logits.detach() if detach else logits, catlas, idx)
         if deep_up:
             return d_style(x_in)
-        maps = [torch.softmax(a, 1)[0][idx].unsqueeze(1) for a in attns]
-        return d_style(x_in, [m.detach() for m in maps] if detach else maps)
+        return d_style(x_in, [attention_pairs(a.detach() if detach else a, idx) for a in attns])
 
     opt = optim.Adam(d_style.parameters(), lr=1e-4)
     opt.zero_grad()
