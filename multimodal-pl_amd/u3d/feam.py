@@ -1,26 +1,30 @@
-"""unet3D_with_feam3 on the native executor (reference unet3D.py:938-1190), forward and backward.
+"""The decoder-level heads of the feam / eam / deepsup models on the native executor (reference unet3D.py:938-1190),
+forward and backward. The models run through trunk.run_model / trunk.TapeFn like every other; this module holds their
+builders and the tape ops those use.
 
-Forward (one autograd Function around the whole model): the shared trunk tape (conv1 .. x1_resb, precls_conv), plus
-at each of the x8 / x4 / x2 decoder levels
+_feam3_forward: the shared trunk tape (conv1 .. x1_resb, precls_conv), plus at each of the x8 / x4 / x2 decoder levels
+what the model's Level record asks for, in this order:
   * deepout{1,2,3} = GN(16) -> ReLU -> Conv3d 1^3 + bias (:969-993, same fused GN-prologue conv as precls_conv);
+  * a detached copy of the feature (feature_stored, :1129);
+  * renew_token (:1051-1068): u3d_renew_token on the feature, in place on the device class token;
   * the EAM attention map against the detached class token (:1131-1175): u3d_eam_prep (token side: LN3, q, M) and
     u3d_eam_attn_fwd (per-voxel LN2 + Nt x C GEMV, written NCDHW), x8/x4/x2 trilinear-upsampled to full size when
-    deep_up (u3d_upsample_trilinear);
-  * a detached copy of the feature (feature_stored, :1129).
-Backward: every output gradient that autograd hands in (unused outputs arrive as None and cost nothing) is pushed
-through the same kernels' backward (u3d_upsample_trilinear_bwd, u3d_eam_attn_bwd, u3d_eam_param_bwd, the 1^3 head
-backward), accumulated into the decoder features' gradients, then the trunk tape replays.
-renew_token (:1051-1068) is u3d_renew_token on the stored features, in place on the device class tokens.
+    deep_up (u3d_upsample_trilinear).
+Each unet3D class states its own three Levels (unet3D_with_feam3 / _feam2 / _deepsup / _feam). Backward: every output
+gradient that autograd hands in (unused outputs arrive as None and cost nothing) is pushed through the same kernels'
+backward (u3d_upsample_trilinear_bwd, u3d_eam_attn_bwd, u3d_eam_param_bwd, the 1^3 head backward) by the closures the
+ops recorded, accumulated into the decoder features' gradients, then the trunk's closures replay.
 
-unet3D_with_eam / unet3D_with_eam_baseline (:431-582, :1370-1504) run the whole EAM (eam_pool_op: the score map and
-the class message cm, u3d_eam_pool_fwd / _bwd) in a cascade down the decoder, each level's cm through a Linear the
-next level's token (run_eam); unet3D_with_feam (:1193-1367) is run_feam3 without the deep heads.
+_eam_forward: unet3D_with_eam / unet3D_with_eam_baseline (:431-582, :1370-1504) run the whole EAM (eam_pool_op: the
+score map and the class message cm, u3d_eam_pool_fwd / _bwd) in a cascade down the decoder, each level's cm through a
+Linear the next level's token.
 """
+from dataclasses import dataclass
+
 import torch
 import torch.nn.functional as F
 
 from . import ops, trunk
-from ._lib import call, query
 
 EAM_KEYS = ("eam84", "eam42", "eam21")
 UP_SCALE = (8, 4, 2)   # upsamplex4 / upsamplex3 / upsamplex2 for deep_up (:1138, :1156, :1175)
@@ -37,7 +41,7 @@ def upsample_trilinear(x, s):
     """NCDHW fp32 [n, c, d, h, w] -> [n, c, sd, sh, sw] (nn.Upsample(scale_factor=s, mode='trilinear'))."""
     n, c, d, h, w = x.shape
     y = torch.empty((n, c, d * s, h * s, w * s), dtype=torch.float32, device=x.device)
-    call("u3d_upsample_trilinear", x.data_ptr(), n * c, d, h, w, s, y.data_ptr(), ops._stream())
+    ops.call("u3d_upsample_trilinear", x.data_ptr(), n * c, d, h, w, s, y.data_ptr(), ops._stream())
     return y
 
 
@@ -46,9 +50,9 @@ def upsample_trilinear_bwd(dy, in_shape, s):
     if dy.dtype != torch.float32 or not dy.is_contiguous():
         dy = dy.float().contiguous()
     dx = torch.empty(in_shape, dtype=torch.float32, device=dy.device)
-    ws = torch.empty(query("u3d_upsample_trilinear_bwd_ws_floats", n * c, d, h, w, s), dtype=torch.float32,
+    ws = torch.empty(ops.query("u3d_upsample_trilinear_bwd_ws_floats", n * c, d, h, w, s), dtype=torch.float32,
                      device=dy.device)
-    call("u3d_upsample_trilinear_bwd", dy.data_ptr(), n * c, d, h, w, s, dx.data_ptr(), 0, ws.data_ptr(),
+    ops.call("u3d_upsample_trilinear_bwd", dy.data_ptr(), n * c, d, h, w, s, dx.data_ptr(), 0, ws.data_ptr(),
          ops._stream())
     return dx
 
@@ -72,11 +76,11 @@ def eam_op(tape, f, key, token, up):
     zhat, q, M = (torch.empty((nt, c), dtype=torch.float32, device=dev) for _ in range(3))
     inv_h = 1.0 / NUM_HEADS
     st = ops._stream()
-    call("u3d_eam_prep", tok.data_ptr(), nt, c, g3.data_ptr(), b3.data_ptr(), wq.data_ptr(), wk.data_ptr(), inv_h,
+    ops.call("u3d_eam_prep", tok.data_ptr(), nt, c, g3.data_ptr(), b3.data_ptr(), wq.data_ptr(), wk.data_ptr(), inv_h,
          zhat.data_ptr(), q.data_ptr(), M.data_ptr(), st)
     att = torch.empty((n, nt, d, h, w), dtype=torch.float32, device=dev)
-    call("u3d_eam_attn_fwd", ops.dt_code(x.dtype), x.data_ptr(), n, v, c, g2.data_ptr(), b2.data_ptr(), M.data_ptr(),
-         nt, att.data_ptr(), st)
+    ops.call("u3d_eam_attn_fwd", ops.dt_code(x.dtype), x.data_ptr(), n, v, c, g2.data_ptr(), b2.data_ptr(),
+             M.data_ptr(), nt, att.data_ptr(), st)
     out = trunk.Act(upsample_trilinear(att, up) if up > 1 else att)
     if tape.record:
         def bwd():
@@ -84,14 +88,14 @@ def eam_op(tape, f, key, token, up):
             if g is None:
                 return
             g = upsample_trilinear_bwd(g, tuple(att.shape), up) if up > 1 else g.float().contiguous()
-            part = torch.empty(query("u3d_eam_attn_bwd_part_floats", n, v, c, nt), dtype=torch.float32, device=dev)
+            part = torch.empty(ops.query("u3d_eam_attn_bwd_part_floats", n, v, c, nt), dtype=torch.float32, device=dev)
             dM = torch.empty((nt, c), dtype=torch.float32, device=dev)
             dg2 = tape.grad_out(key + ".norm2.weight", g2)
             db2 = tape.grad_out(key + ".norm2.bias", b2)
             acc = f.grad is not None
             dx = f.grad if acc else torch.empty_like(x)
             s = ops._stream()
-            call("u3d_eam_attn_bwd", ops.dt_code(x.dtype), x.data_ptr(), n, v, c, g2.data_ptr(), b2.data_ptr(),
+            ops.call("u3d_eam_attn_bwd", ops.dt_code(x.dtype), x.data_ptr(), n, v, c, g2.data_ptr(), b2.data_ptr(),
                  M.data_ptr(), nt, g.data_ptr(), dx.data_ptr(), int(acc), part.data_ptr(), dM.data_ptr(),
                  dg2.data_ptr(), db2.data_ptr(), 0, s)
             f.grad = dx
@@ -100,7 +104,7 @@ def eam_op(tape, f, key, token, up):
             dg3 = tape.grad_out(key + ".norm3.weight", g3)
             db3 = tape.grad_out(key + ".norm3.bias", b3)
             dq_ws, dz_ws = torch.empty((nt, c), dtype=torch.float32, device=dev), torch.empty_like(dM)
-            call("u3d_eam_param_bwd", dM.data_ptr(), nt, c, zhat.data_ptr(), g3.data_ptr(), b3.data_ptr(),
+            ops.call("u3d_eam_param_bwd", dM.data_ptr(), nt, c, zhat.data_ptr(), g3.data_ptr(), b3.data_ptr(),
                  wq.data_ptr(), wk.data_ptr(), q.data_ptr(), inv_h, dq_ws.data_ptr(), dz_ws.data_ptr(),
                  dwq.data_ptr(), dkv.data_ptr(), dg3.data_ptr(), db3.data_ptr(), 0, s)
             for nm in (".norm2.weight", ".norm2.bias", ".q.weight", ".kv.weight", ".norm3.weight", ".norm3.bias"):
@@ -174,9 +178,10 @@ def eam_pool_op(tape, f, key, tok):
     with torch.no_grad():
         A = _pool_before(tok.t, g3, b3, wq, kv[:c]).contiguous()
     att, yhat, stat = new(n, nt, d, h, w), new(rows, c), new(2 * rows)
-    npart = query("u3d_eam_pool_part_floats", v, c, nt)
-    call("u3d_eam_pool_fwd", ops.dt_code(x.dtype), x.data_ptr(), n, v, c, g2.data_ptr(), b2.data_ptr(), A.data_ptr(), nt,
-         NUM_HEADS, scale, att.data_ptr(), yhat.data_ptr(), stat.data_ptr(), new(npart).data_ptr(), ops._stream())
+    npart = ops.query("u3d_eam_pool_part_floats", v, c, nt)
+    ops.call("u3d_eam_pool_fwd", ops.dt_code(x.dtype), x.data_ptr(), n, v, c, g2.data_ptr(), b2.data_ptr(),
+             A.data_ptr(), nt, NUM_HEADS, scale, att.data_ptr(), yhat.data_ptr(), stat.data_ptr(),
+             new(npart).data_ptr(), ops._stream())
     with torch.no_grad():
         cm = Tok(_pool_after(yhat, g2, b2, kv[c:], pw, pb))
     out = trunk.Act(att)
@@ -200,7 +205,7 @@ def eam_pool_op(tape, f, key, tok):
             acc = f.grad is not None
             dx = f.grad if acc else torch.empty_like(x)
             ptr = lambda t: t.data_ptr() if t is not None else 0       # noqa: E731
-            call("u3d_eam_pool_bwd", ops.dt_code(x.dtype), x.data_ptr(), n, v, c, g2.data_ptr(), b2.data_ptr(),
+            ops.call("u3d_eam_pool_bwd", ops.dt_code(x.dtype), x.data_ptr(), n, v, c, g2.data_ptr(), b2.data_ptr(),
                  A.data_ptr(), nt, NUM_HEADS, scale, stat.data_ptr(), ptr(dy), ptr(dd), ptr(gatt), dx.data_ptr(),
                  int(acc), new(npart).data_ptr(), dA.data_ptr(), dg2.data_ptr(), db2.data_ptr(), 0, ops._stream())
             f.grad = dx
@@ -235,12 +240,13 @@ def tok_linear(tape, tok, key):
 EAM_LINEAR_KEYS = ("linear84_2_42", "linear42_2_21")
 
 
-def _eam_forward(tape, cfg, x, gates, train):
-    """unet3D_with_eam / _eam_baseline (unet3D.py:508-582, :1440-1504): the trunk, and in training the cascade of EAMs
-    down the decoder, each level's class message through a Linear the next level's token. gates[k]: level k runs (the
-    reference's cumulative use_cm tests). Returns (logits Act, last cm Tok or None, [map Act])."""
+def _eam_forward(tape, cfg, x, gates):
+    """unet3D_with_eam / _eam_baseline (unet3D.py:508-582, :1440-1504): the trunk, then the cascade of EAMs down the
+    decoder, each level's class message through a Linear the next level's token. gates[k]: level k runs (the
+    reference's cumulative use_cm tests; () in eval: the trunk and the logits head alone). Returns the logits Act and
+    the outputs {cm: the last level's Tok, if a level ran; atten: the map Acts}."""
     root = None
-    if train and gates[0]:
+    if gates and gates[0]:
         root = Tok(tape.P["class_token"].detach())
         if tape.record:
             def bwd():   # recorded first, so it runs last: every level has added its share by then
@@ -251,122 +257,55 @@ def _eam_forward(tape, cfg, x, gates, train):
     lg = tape.head(f, cfg)
     cm, att = None, []
     for k, on in enumerate(gates):
-        if not (train and on):
+        if not on:
             break
         tok = root if k == 0 else tok_linear(tape, cm, EAM_LINEAR_KEYS[k - 1])
         a, cm = eam_pool_op(tape, tape.dec[k], EAM_KEYS[k], tok)
         att.append(a)
-    return lg, cm, att
-
-
-class _EamFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, cfg, dtype, gates, names, x, *tensors):
-        ctx.set_materialize_grads(False)
-        tape = trunk.Tape.recording(names, tensors, dtype)
-        lg, cm, att = _eam_forward(tape, cfg, x, gates, True)
-        ctx.state = (tape, lg, cm, att)
-        ctx.names = names
-        return tuple([_ncdhw(lg.t)] + ([cm.t.unsqueeze(0)] if cm is not None else []) + [a.t for a in att])
-
-    @staticmethod
-    def backward(ctx, *grads):
-        tape, lg, cm, att = ctx.state
-        g_lg = grads[0]
-        if cm is not None:
-            cm.grad = grads[1].reshape(cm.t.shape).float() if grads[1] is not None else None
-            for a, g in zip(att, grads[2:]):
-                a.grad = g.contiguous() if g is not None else None
-        pg = _backward(tape, lg, g_lg, ctx.names)
-        ctx.state = None
-        return (None, None, None, None, None, *pg)
+    return lg, {"cm": (trunk.TOKEN, [cm] if cm is not None else []), "atten": (trunk.NCDHW, att)}
 
 
 def run_eam(model, x, gates):
     """model: unet3D.unet3D_with_eam / unet3D_with_eam_baseline. train: (logits, cm [1, nt, C] or None, atten_map);
     eval: logits (the EAMs are not run)."""
-    ops.require_device(x)
-    cfg = model._u3d_cfg
-    dtype = trunk.compute_dtype(getattr(model, "compute_dtype", None))
-    x = x.float().contiguous()
-    named = list(model.named_parameters())
-    gates = tuple(bool(g) for g in gates)
-    if model.training and torch.is_grad_enabled() and any(p.requires_grad for _, p in named):
-        outs = _EamFn.apply(cfg, dtype, gates, [nm for nm, _ in named], x, *[p for _, p in named])
-        if not gates[0]:
-            return outs[0], None, []
-        return outs[0], outs[1], list(outs[2:])
-    with torch.no_grad():
-        tape = trunk.Tape(dict(named), dtype, record=False)
-        lg, cm, att = _eam_forward(tape, cfg, x, gates, model.training)
+    gates = tuple(bool(g) for g in gates) if model.training else ()
+    lg, outs = trunk.run_model(lambda tape, x: _eam_forward(tape, model._u3d_cfg, x, gates), x,
+                               list(model.named_parameters()), getattr(model, "compute_dtype", None),
+                               grad=model.training)
     if not model.training:
-        return _ncdhw(lg.t)
-    return _ncdhw(lg.t), cm.t.unsqueeze(0) if cm is not None else None, [a.t for a in att]
+        return lg
+    return lg, outs["cm"][0] if outs["cm"] else None, outs["atten"]
 
 
-def _feam3_forward(tape, cfg, x, tokens, use_cm, deep_up, heads=True, renew=None, store=True, deep_heads=True):
-    """renew = (mask, num_classes, alpha): unet3D_with_feam2's in-forward class-token update of each level, before
-    that level's attention (unet3D.py:869-878, 896-903, 919-926). store=False: no detached feature copies
-    (unet3D_with_deepsup, unet3D.py:370-429: the trunk and the three deep-supervision heads alone). deep_heads=False:
-    no deepout heads (unet3D_with_feam, unet3D.py:1272-1367: the renewed tokens and the attention maps alone)."""
+@dataclass(frozen=True)
+class Level:
+    """What a model does with the decoder feature after x8 / x4 / x2_resb, in the order it happens there."""
+    deep: bool = False     # the deep-supervision head deepout{1,2,3} (unet3D.py:969-993)
+    store: bool = False    # a detached copy of the feature (feature_stored, :1129)
+    renew: tuple = None    # (mask, classes, alpha): ``token`` updated in place from the feature first (:869-878)
+    token: object = None   # the level's class token [classes - 1, C]
+    attend: bool = False   # the EAM attention map against the detached token (:1131-1175)
+    up: int = 1            # the map trilinear-upsampled by this factor (deep_up)
+
+
+def _feam3_forward(tape, cfg, x, levels):
+    """The trunk, the logits head and, per decoder level, what its Level asks for (none in eval). Returns the logits
+    Act and the outputs {atten, deep, stored}."""
     f, _ = tape.trunk(x, cfg)
     lg = tape.head(f, cfg)
     att, deep, feats = [], [], []
-    if heads:
-        for k in range(3):
-            fk = tape.dec[k]
-            if deep_heads:
-                deep.append(tape.gn_conv(fk, f"deepout{k + 1}.2", 1, 1, gn_key=f"deepout{k + 1}.0", G=16, bias=True,
-                                         out_f32=True, standardize=False))
-            if store:
-                feats.append(fk.t.detach().clone())
-            if renew is not None:
-                renew_token([tokens[k]], [fk.t.permute(0, 4, 1, 2, 3)], renew[0], renew[1], renew[2])
-            if use_cm[k]:
-                att.append(eam_op(tape, fk, EAM_KEYS[k], tokens[k], UP_SCALE[k] if deep_up else 1))
-    return lg, att, deep, feats
-
-
-def _ncdhw(t):
-    return t.permute(0, 4, 1, 2, 3)
-
-
-def _backward(tape, lg, g_lg, names):
-    """Replay ``tape`` from the logits' NCDHW gradient (None: no loss reads them, zeros) -> parameter gradients."""
-    if g_lg is None:
-        g_lg = torch.zeros(lg.t.shape, dtype=torch.float32, device=lg.t.device)
-    else:
-        g_lg = trunk.ndhwc_grad(g_lg)
-    tape.backward(lg, g_lg)
-    return tape.finish(names)
-
-
-class _Feam3Fn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, cfg, dtype, use_cm, deep_up, store, deep_heads, names, x, tokens, *tensors):
-        ctx.set_materialize_grads(False)
-        tape = trunk.Tape.recording(names, tensors, dtype)
-        lg, att, deep, feats = _feam3_forward(tape, cfg, x, tokens, use_cm, deep_up, store=store,
-                                              deep_heads=deep_heads)
-        ctx.state = (tape, lg, att, deep)
-        ctx.names = names
-        ctx.n_att = len(att)
-        fo = [_ncdhw(ft) for ft in feats]
-        ctx.mark_non_differentiable(*fo)
-        return tuple([_ncdhw(lg.t)] + [a.t for a in att] + [_ncdhw(d.t) for d in deep] + fo)
-
-    @staticmethod
-    def backward(ctx, *grads):
-        tape, lg, att, deep = ctx.state
-        na = ctx.n_att
-        g_lg = grads[0]
-        for a, g in zip(att, grads[1:1 + na]):
-            a.grad = g.contiguous() if g is not None else None
-        for d, g in zip(deep, grads[1 + na:1 + na + len(deep)]):
-            d.grad = trunk.ndhwc_grad(g) if g is not None else None
-        pg = _backward(tape, lg, g_lg, ctx.names)
-        ctx.state = None
-        return (None, None, None, None, None, None, None, None, None, *pg)
+    for k, lv in enumerate(levels):
+        fk = tape.dec[k]
+        if lv.deep:
+            deep.append(tape.gn_conv(fk, f"deepout{k + 1}.2", 1, 1, gn_key=f"deepout{k + 1}.0", G=16, bias=True,
+                                     out_f32=True, standardize=False))
+        if lv.store:
+            feats.append(fk.t.detach().clone())
+        if lv.renew is not None:
+            renew_token([lv.token], [trunk.ncdhw(fk.t)], *lv.renew)
+        if lv.attend:
+            att.append(eam_op(tape, fk, EAM_KEYS[k], lv.token, lv.up))
+    return lg, {"atten": (trunk.NCDHW, att), "deep": (trunk.NDHWC, deep), "stored": (trunk.STORED, feats)}
 
 
 def labels_reach(mask, sizes, ncls):
@@ -377,39 +316,20 @@ def labels_reach(mask, sizes, ncls):
     return any(bool(F.interpolate(valid, s, mode="nearest").any()) for s in sizes)
 
 
-def run_feam3(model, x, renew=None, eam=True, deep_heads=True, gates=None):
-    """model: unet3D.unet3D_with_feam3 (or _feam2). Returns train: (logits, atten_map, deep_map, feature_stored);
-    eval: logits. eam=False: unet3D.unet3D_with_deepsup, the same graph without the EAMs, the class tokens and the
-    stored features (atten_map and feature_stored come back empty; any batch size). deep_heads=False:
-    unet3D.unet3D_with_feam, no deepout heads and no stored features (deep_map and feature_stored come back empty);
-    gates: which levels run their EAM, instead of model.use_cm (the reference's cumulative tests there)."""
+def run_feam3(model, x, levels):
+    """model: unet3D.unet3D_with_feam3 / _feam2 / _deepsup / _feam, ``levels`` its three Levels (x8, x4, x2). Returns
+    train: (logits, atten_map, deep_map, feature_stored), each list as long as the levels make it; eval: logits."""
     ops.require_device(x)
-    cfg = model._u3d_cfg
-    dtype = trunk.compute_dtype(getattr(model, "compute_dtype", None))
-    x = x.float().contiguous()
-    tokens = [model.class_token1, model.class_token2, model.class_token3] if eam else None
-    use_cm = tuple(bool(u) and eam for u in (model.use_cm if gates is None else gates))
-    store, nd = eam and deep_heads, 3 if deep_heads else 0
-    deep_up = bool(eam and model.deep_up)
     named = list(model.named_parameters())
     if not model.training:
-        with torch.no_grad():
-            tape = trunk.Tape(dict(named), dtype, record=False)
-            lg, _, _, _ = _feam3_forward(tape, cfg, x, tokens, use_cm, deep_up, heads=False)
-        return _ncdhw(lg.t)
-    if torch.is_grad_enabled() and any(p.requires_grad for _, p in named):
-        if renew is not None:
-            raise RuntimeError("a leaf Variable that requires grad is being used in an in-place operation.")
-        outs = _Feam3Fn.apply(cfg, dtype, use_cm, deep_up, store, deep_heads, [nm for nm, _ in named], x, tokens,
-                              *[p for _, p in named])
-    else:
-        with torch.no_grad():
-            tape = trunk.Tape(dict(named), dtype, record=False)
-            lg, att, deep, feats = _feam3_forward(tape, cfg, x, tokens, use_cm, deep_up, renew=renew, store=store,
-                                                  deep_heads=deep_heads)
-        outs = [_ncdhw(lg.t)] + [a.t for a in att] + [_ncdhw(d.t) for d in deep] + [_ncdhw(ft) for ft in feats]
-    na = sum(use_cm)
-    return outs[0], list(outs[1:1 + na]), list(outs[1 + na:1 + na + nd]), list(outs[1 + na + nd:])
+        levels = ()
+    elif any(lv.renew is not None for lv in levels) and trunk.wants_grad([p for _, p in named]):
+        raise RuntimeError("a leaf Variable that requires grad is being used in an in-place operation.")
+    lg, outs = trunk.run_model(lambda tape, x: _feam3_forward(tape, model._u3d_cfg, x, levels), x, named,
+                               getattr(model, "compute_dtype", None), grad=model.training)
+    if not model.training:
+        return lg
+    return lg, outs["atten"], outs["deep"], outs["stored"]
 
 
 def renew_token(tokens, features, mask, num_classes, alpha):
@@ -433,7 +353,7 @@ def renew_token(tokens, features, mask, num_classes, alpha):
         if feat.dtype not in (torch.float32, torch.bfloat16):
             feat = feat.float()
         ops.require_device(feat)
-        ws = ops.WS.get(query("u3d_renew_token_ws_bytes", n, d, h, w, num_classes, c), feat.device,
+        ws = ops.WS.get(ops.query("u3d_renew_token_ws_bytes", n, d, h, w, num_classes, c), feat.device,
                         ops.Slot.RENEW_TOKEN)
-        call("u3d_renew_token", ops.dt_code(feat.dtype), feat.data_ptr(), sv, sc, n, d, h, w, c, mask.data_ptr(),
+        ops.call("u3d_renew_token", ops.dt_code(feat.dtype), feat.data_ptr(), sv, sc, n, d, h, w, c, mask.data_ptr(),
              md, mh, mw, num_classes, tok.shape[0], float(alpha), tok.data_ptr(), ws.data_ptr(), ops._stream())

@@ -30,7 +30,7 @@ def class_weights(mask, C, device):
 
 class DeferredLossGrad(torch.Tensor):
     """The partial loss's gradient w.r.t. the trunk's logits, handed back unformed when the logits came straight from
-    the streaming head (trunk._TrunkFn tags them): the trunk's backward passes it to the head, whose backward forms the
+    the streaming head (trunk.TapeFn tags them): the trunk's backward passes it to the head, whose backward forms the
     loss gradient in registers (ops.head_loss_bwd) — the fp32 dlogits tensor (113 MB at 2 x 96^3 x 16) is never
     written or read. Anything else that touches it (a hook, torch.autograd.grad on the logits, a sum with another
     gradient) goes through __torch_dispatch__, which forms the real gradient first (ops.partial_loss_bwd): every

@@ -6,6 +6,10 @@ weights; weight standardisation is re-applied from the fp32 master each step (un
 Graph (reference unet3D.forward :1734-1806 / unet3D_baseline.forward :663-718 / unet3D_g.forward :1568-1623):
   stem conv1 (or conv0 s2 -> conv1) -> layer0..4 (NoBottleneck :40-73) -> fusionConv (GN,ReLU,1^3)
   -> 4 x [trilinear x2 + skip -> x{8,4,2,1}_resb] -> precls_conv (GN,ReLU,1^3+bias) [-> x2 upsample (unet3D_g)]
+
+Every model class of unet3D.py reaches autograd through one Function, TapeFn, and one runner, run_model: a model is a
+builder (tape, x) -> outputs (run_trunk here, dynhead._dyn_forward, feam._feam3_forward, feam._eam_forward), and what
+differs between models is what their builders append to the tape.
 """
 from dataclasses import dataclass
 from functools import partial
@@ -49,10 +53,12 @@ class Tape:
         self.sink = None
         self.std = True
         self.pending = []   # weight grads waiting for the batched standardisation backward
+        self.head_out = None            # the Act of a 16-class streaming head (conv_fwd_form)
+        self.offer_head_link = False    # the builder lets the loss hand its gradient to that head unformed (TapeFn)
 
     @classmethod
     def recording(cls, names, tensors, dtype):
-        """A recording tape over the named parameters for one autograd Function, attached to the current DDP sink."""
+        """A recording tape over the named parameters for one model step (TapeFn), attached to the current DDP sink."""
         from .ddp import current_sink
         tape = cls(dict(zip(names, tensors)), dtype, record=True)
         tape.sink = current_sink()
@@ -173,7 +179,7 @@ class Tape:
             y = ops.conv_fwd(x, pf, cout, k, stride, gn, res)
         out = Act(y)
         if head and cout == 16:
-            self.head_out = out  # the partial loss may hand its gradient to this head unformed (_TrunkFn)
+            self.head_out = out  # the partial loss may hand its gradient to this head unformed (TapeFn)
         if st16 is not None:
             out.stats[16] = st16  # GroupNorm(16) statistics from the conv epilogue (consumed by the next GN)
         return out, xn
@@ -360,46 +366,96 @@ def ndhwc_grad(g, dtype=torch.float32):
     return g.permute(0, 2, 3, 4, 1).to(dtype).contiguous()
 
 
-class _TrunkFn(torch.autograd.Function):
+def ncdhw(t):
+    return t.permute(0, 4, 1, 2, 3)
+
+
+# How a builder's output crosses the autograd boundary: kind -> (what autograd sees of it, its incoming gradient in
+# the form the tape reads; None: not differentiable).
+NDHWC, NCDHW, TOKEN, STORED = "ndhwc", "ncdhw", "token", "stored"
+CROSS = {
+    NDHWC: (lambda a: ncdhw(a.t), ndhwc_grad),                             # an NDHWC Act: logits, deep maps
+    NCDHW: (lambda a: a.t, lambda g: g.contiguous()),                      # an NCDHW fp32 Act: attention maps
+    TOKEN: (lambda k: k.t.unsqueeze(0), lambda g: g.squeeze(0).float()),   # a feam.Tok [nt, C]: the class message
+    STORED: (ncdhw, None),                                                 # a detached tensor: feature_stored
+}
+
+
+def wants_grad(tensors):
+    return torch.is_grad_enabled() and any(p.requires_grad for p in tensors)
+
+
+class TapeFn(torch.autograd.Function):
+    """The one Function between autograd and a whole model step. ``build(tape, x)`` runs the forward on a recording
+    tape and returns its outputs [(kind, value)], the primary one (NDHWC: what seeds the tape's replay) first."""
+
     @staticmethod
-    def forward(ctx, cfg, dtype, names, x, *tensors):
+    def forward(ctx, build, dtype, names, x, *tensors):
+        ctx.set_materialize_grads(False)  # an output no loss reads arrives as None and costs nothing
         tape = Tape.recording(names, tensors, dtype)
-        f, _ = tape.trunk(x, cfg)
-        lg = tape.head(f, cfg)
-        ctx.tape, ctx.out, ctx.names = tape, lg, names
-        out = lg.t.permute(0, 4, 1, 2, 3)
+        outs = build(tape, x)
+        ctx.tape, ctx.outs, ctx.names = tape, outs, names
+        seen = [CROSS[kind][0](v) for kind, v in outs]
+        ctx.mark_non_differentiable(*[t for t, (kind, _) in zip(seen, outs) if CROSS[kind][1] is None])
+        # The partial loss may hand its gradient back unformed (loss.DeferredLossGrad) where the logits come straight
+        # from the streaming head, and only to the models whose builder offers it (run_trunk). Offering it to the
+        # feam / eam / deepsup models would change their launches (ops.head_loss_bwd for ops.head_bwd): a performance
+        # change for a pull request of its own.
         ctx.link = None
-        if getattr(tape, "head_out", None) is lg:  # logits straight from the streaming head (no final upsample)
-            ctx.link = object()
-            out._u3d_head_link = ctx.link  # the partial loss hands its gradient back unformed (loss.DeferredLossGrad)
-        return out
+        if tape.offer_head_link and tape.head_out is outs[0][1]:
+            ctx.link = seen[0]._u3d_head_link = object()
+        return tuple(seen)
 
     @staticmethod
-    def backward(ctx, g):
-        tape = ctx.tape
-        if isinstance(g, DeferredLossGrad) and ctx.link is not None and g.link is ctx.link and g.unformed():
-            tape.backward(ctx.out, g)  # to the head's backward as is (ops.head_loss_bwd)
+    def backward(ctx, g, *grads):
+        tape, outs = ctx.tape, ctx.outs
+        for (kind, v), gv in zip(outs[1:], grads):
+            if CROSS[kind][1] is not None:
+                v.grad = CROSS[kind][1](gv) if gv is not None else None
+        out = outs[0][1]
+        if isinstance(g, DeferredLossGrad):
+            if not (ctx.link is not None and g.link is ctx.link and g.unformed()):
+                g = ndhwc_grad(g.materialize())  # (else: to the head's backward as is, ops.head_loss_bwd)
+        elif g is None:  # no loss reads the primary output
+            g = torch.zeros(out.t.shape, dtype=torch.float32, device=out.t.device)
         else:
-            if isinstance(g, DeferredLossGrad):
-                g = g.materialize()
-            tape.backward(ctx.out, ndhwc_grad(g))
-        grads = tape.finish(ctx.names)
-        ctx.tape = ctx.out = None
-        return (None, None, None, None, *grads)
+            g = ndhwc_grad(g)
+        tape.backward(out, g)
+        pg = tape.finish(ctx.names)
+        ctx.tape = ctx.outs = None
+        return (*[None] * (len(ctx.needs_input_grad) - len(pg)), *pg)
 
 
-def run_trunk(cfg, x, named_params, dtype=None):
-    """Forward the trunk + classification head. Returns NCDHW-shaped fp32 logits (NDHWC storage)."""
-    dtype = compute_dtype(dtype)
+def run_model(build, x, named_params, dtype=None, grad=True):
+    """One model step on the native executor. ``build(tape, x)`` -> (primary output Act, {name: (kind, [values])});
+    returns (the primary output NCDHW, {name: [tensors]}). Records under autograd when a parameter asks for a gradient
+    (``grad`` false: never, an eval forward), else runs the same builder on a tape that records nothing."""
     ops.require_device(x)
+    dtype = compute_dtype(dtype)
     if x.dtype != torch.float32 or not x.is_contiguous():
         x = x.float().contiguous()
     names = [n for n, _ in named_params]
     tensors = [p for _, p in named_params]
-    if torch.is_grad_enabled() and any(p.requires_grad for p in tensors):
-        return _TrunkFn.apply(cfg, dtype, names, x, *tensors)
-    with torch.no_grad():
-        tape = Tape(dict(zip(names, tensors)), dtype, record=False)
+    sizes = {}
+
+    def flat(tape, x):
+        out, groups = build(tape, x)
+        sizes.update((name, len(vs)) for name, (_, vs) in groups.items())
+        return [(NDHWC, out)] + [(kind, v) for kind, vs in groups.values() for v in vs]
+
+    if grad and wants_grad(tensors):
+        seen = TapeFn.apply(flat, dtype, names, x, *tensors)
+    else:
+        with torch.no_grad():
+            seen = [CROSS[kind][0](v) for kind, v in flat(Tape(dict(zip(names, tensors)), dtype, record=False), x)]
+    rest = iter(seen[1:])
+    return seen[0], {name: [next(rest) for _ in range(n)] for name, n in sizes.items()}
+
+
+def run_trunk(cfg, x, named_params, dtype=None):
+    """Forward the trunk + classification head. Returns NCDHW-shaped fp32 logits (NDHWC storage)."""
+    def build(tape, x):
         f, _ = tape.trunk(x, cfg)
-        lg = tape.head(f, cfg)
-        return lg.t.permute(0, 4, 1, 2, 3)
+        tape.offer_head_link = True  # these logits may take the partial loss's gradient unformed (TapeFn)
+        return tape.head(f, cfg), {}
+    return run_model(build, x, named_params, dtype)[0]

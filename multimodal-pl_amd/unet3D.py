@@ -102,10 +102,19 @@ def _make_layer(model, block, inplanes, planes, blocks, stride=(1, 1, 1), dilati
     return nn.Sequential(*layers)
 
 
+def _head(groups, cin, ncls):
+    return nn.Sequential(nn.GroupNorm(groups, cin), nn.ReLU(inplace=in_place), nn.Conv3d(cin, ncls, kernel_size=1))
+
+
 class _TrunkMixin:
     """Builds the conv1 / layer0-4 / fusionConv / decoder / precls_conv modules with reference names."""
 
-    def _build_trunk(self, in_channel, f, layers, group, fusion_group, head_group, ncls, conv0=False):
+    def _build_trunk(self, in_channel, f, layers, group, fusion_group, head_group, ncls, conv0=False, up48=False,
+                     deep=False, eams=0, linears=0):
+        """Every trunk class's modules in the reference's registration (and construction) order. What a class has
+        after x8 / x4 / x2_resb: a deep-supervision head deepout{1,2,3} (``deep``), an EAM (the first ``eams`` levels),
+        the Linear that hands the class message down a level (the first ``linears``). ``up48``: the x4 / x8 upsamplers
+        of deep_up, registered before the decoder (:964-965)."""
         if conv0:
             self.conv0 = conv3x3x3(in_channel, f, stride=[2, 2, 2], weight_std=self.weight_std)
             self.conv1 = conv3x3x3(f, f, stride=[1, 1, 1], weight_std=self.weight_std)
@@ -124,22 +133,35 @@ class _TrunkMixin:
             conv3x3x3(8 * f, 8 * f, kernel_size=(1, 1, 1), padding=(0, 0, 0), weight_std=self.weight_std),
         )
         self.upsamplex2 = nn.Upsample(scale_factor=2, mode="trilinear")
-        self.x8_resb = mk(8 * f, 4 * f, 1, (1, 1, 1))
-        self.x4_resb = mk(4 * f, 2 * f, 1, (1, 1, 1))
-        self.x2_resb = mk(2 * f, f, 1, (1, 1, 1))
+        if up48:
+            self.upsamplex3 = nn.Upsample(scale_factor=4, mode="trilinear")
+            self.upsamplex4 = nn.Upsample(scale_factor=8, mode="trilinear")
+        for k, (name, cin, cout) in enumerate((("x8_resb", 8 * f, 4 * f), ("x4_resb", 4 * f, 2 * f),
+                                               ("x2_resb", 2 * f, f))):
+            setattr(self, name, mk(cin, cout, 1, (1, 1, 1)))
+            if deep:
+                setattr(self, f"deepout{k + 1}", _head(16, cout, ncls))
+            if k < eams:
+                setattr(self, ("eam84", "eam42", "eam21")[k], EAM(cout, input_resolution=None, num_heads=4))
+            if k < linears:
+                setattr(self, ("linear84_2_42", "linear42_2_21")[k], nn.Linear(cout, cout // 2))
         self.x1_resb = mk(f, f, 1, (1, 1, 1))
-        self.precls_conv = nn.Sequential(
-            nn.GroupNorm(head_group, f),
-            nn.ReLU(inplace=in_place),
-            nn.Conv3d(f, ncls, kernel_size=1),
-        )
+        self.precls_conv = _head(head_group, f, ncls)
         self._u3d_cfg = trunk.TrunkCfg(layers=tuple(layers), groups=group, fusion_groups=fusion_group,
                                        head_groups=head_group, conv0=conv0, final_up=conv0,
                                        weight_std=bool(self.weight_std))
 
-    def _make_layer(self, block, inplanes, planes, blocks, stride=(1, 1, 1), dilation=1, multi_grid=1):
-        return _make_layer(self, block, inplanes, planes, blocks, stride, dilation, multi_grid,
-                           group=self._u3d_cfg.groups if hasattr(self, "_u3d_cfg") else 16)
+    def _ema_detach(self, ema):
+        if ema:
+            for param in self.parameters():
+                param.detach_()
+
+    def _tokens_to(self, dev):
+        """The three class tokens, moved to ``dev`` where they are plain tensors."""
+        self.class_token1 = self.class_token1.to(dev)
+        self.class_token2 = self.class_token2.to(dev)
+        self.class_token3 = self.class_token3.to(dev)
+        return [self.class_token1, self.class_token2, self.class_token3]
 
     def _trunk_params(self):
         return [(n, p) for n, p in self.named_parameters()
@@ -164,9 +186,7 @@ class unet3D_baseline(_TrunkMixin, nn.Module):
         self._build_trunk(1, 32, layers, 16, 16, 16, num_classes)
         self.upsamplex3 = nn.Upsample(scale_factor=4, mode="trilinear")
         self.upsamplex4 = nn.Upsample(scale_factor=8, mode="trilinear")
-        if ema:
-            for param in self.parameters():
-                param.detach_()
+        self._ema_detach(ema)
 
     def forward(self, input, mask=None):
         logits = self._run(input)
@@ -247,36 +267,6 @@ class EAM(nn.Module):
                        "on the hot path")
 
 
-def _build_deep_trunk(self, layers, num_classes, eam):
-    """The modules unet3D_with_feam3 (:958-1014) and unet3D_with_deepsup (:288-341) share, in the reference's
-    registration order: the trunk with a deep-supervision head deepout{1,2,3} after x8 / x4 / x2_resb and, with
-    ``eam``, an EAM after each head (plus the x4 / x8 upsamplers of deep_up)."""
-    mk = lambda cin, cout, n, s: _make_layer(self, NoBottleneck, cin, cout, n, stride=s)  # noqa: E731
-    self.conv1 = conv3x3x3(1, 32, stride=[1, 1, 1], weight_std=self.weight_std)
-    self.layer0 = mk(32, 32, layers[0], (1, 1, 1))
-    self.layer1 = mk(32, 64, layers[1], (2, 2, 2))
-    self.layer2 = mk(64, 128, layers[2], (2, 2, 2))
-    self.layer3 = mk(128, 256, layers[3], (2, 2, 2))
-    self.layer4 = mk(256, 256, layers[4], (2, 2, 2))
-    self.fusionConv = nn.Sequential(
-        nn.GroupNorm(16, 256), nn.ReLU(inplace=in_place),
-        conv3x3x3(256, 256, kernel_size=(1, 1, 1), padding=(0, 0, 0), weight_std=self.weight_std))
-    self.upsamplex2 = nn.Upsample(scale_factor=2, mode="trilinear")
-    if eam:
-        self.upsamplex3 = nn.Upsample(scale_factor=4, mode="trilinear")
-        self.upsamplex4 = nn.Upsample(scale_factor=8, mode="trilinear")
-    head = lambda c: nn.Sequential(nn.GroupNorm(16, c), nn.ReLU(inplace=in_place),  # noqa: E731
-                                   nn.Conv3d(c, num_classes, kernel_size=1))
-    for k, (name, cin, cout, ekey) in enumerate((("x8_resb", 256, 128, "eam84"), ("x4_resb", 128, 64, "eam42"),
-                                                 ("x2_resb", 64, 32, "eam21"))):
-        setattr(self, name, mk(cin, cout, 1, (1, 1, 1)))
-        setattr(self, f"deepout{k + 1}", head(cout))
-        if eam:
-            setattr(self, ekey, EAM(cout, input_resolution=None, num_heads=4))
-    self.x1_resb = mk(32, 32, 1, (1, 1, 1))
-    self.precls_conv = head(32)
-
-
 class unet3D_with_feam3(_TrunkMixin, nn.Module):
     """Reference unet3D.py:938-1190 (the model train_amos_atlas_final.py:118 trains): the trunk + deep-supervision
     heads deepout1-3 + EAM attention maps against EMA class tokens. forward(input, mask=None) -> train:
@@ -292,32 +282,27 @@ class unet3D_with_feam3(_TrunkMixin, nn.Module):
         self.alpha = 0.01
         self.deep_up = deep_up
         super().__init__()
-        _build_deep_trunk(self, layers, num_classes, eam=True)
+        self._build_trunk(1, 32, layers, 16, 16, 16, num_classes, up48=True, deep=True, eams=3)
         # class tokens: plain tensors (not parameters / buffers, so not in the state_dict), :1016-1021
         self.class_token1 = torch.randn(num_classes - 1, 128)
         self.class_token2 = torch.randn(num_classes - 1, 64)
         self.class_token3 = torch.randn(num_classes - 1, 32)
-        self._u3d_cfg = trunk.TrunkCfg(layers=tuple(layers), weight_std=bool(self.weight_std))
-        if ema:
-            for param in self.parameters():
-                param.detach_()
+        self._ema_detach(ema)
 
     def renew_token(self, features, mask):
         """EMA update of the class tokens from the stored features (:1051-1068), on the device."""
         from u3d import feam
-        dev = mask.device
-        self.class_token1 = self.class_token1.to(dev)
-        self.class_token2 = self.class_token2.to(dev)
-        self.class_token3 = self.class_token3.to(dev)
-        feam.renew_token([self.class_token1, self.class_token2, self.class_token3], features, mask,
-                         self.num_classes, self.alpha)
+        feam.renew_token(self._tokens_to(mask.device), features, mask, self.num_classes, self.alpha)
+
+    def _levels(self, tokens, renew=None):
+        """Per decoder level: the deep head, the stored feature, the map where use_cm (full size if deep_up)."""
+        from u3d import feam
+        return [feam.Level(deep=True, store=True, renew=renew, token=tokens[k], attend=bool(self.use_cm[k]),
+                           up=feam.UP_SCALE[k] if self.deep_up else 1) for k in range(3)]
 
     def forward(self, input, mask=None):
         from u3d import feam
-        self.class_token1 = self.class_token1.to(input.device)
-        self.class_token2 = self.class_token2.to(input.device)
-        self.class_token3 = self.class_token3.to(input.device)
-        return feam.run_feam3(self, input)
+        return feam.run_feam3(self, input, self._levels(self._tokens_to(input.device)))
 
 
 class unet3D_with_feam2(unet3D_with_feam3):
@@ -333,21 +318,15 @@ class unet3D_with_feam2(unet3D_with_feam3):
         self.class_token1 = nn.Parameter(torch.randn(num_classes - 1, 128))
         self.class_token2 = nn.Parameter(torch.randn(num_classes - 1, 64))
         self.class_token3 = nn.Parameter(torch.randn(num_classes - 1, 32))
-        if ema:
-            for param in self.parameters():
-                param.detach_()
-
-    def _trunk_named(self):
-        return [(n, p) for n, p in self.named_parameters() if not n.startswith("class_token")]
+        self._ema_detach(ema)
 
     def forward(self, input, mask=None):
         from u3d import feam
-        if not self.training:
-            return feam.run_feam3(self, input)
-        if mask is None:
+        if self.training and mask is None:
             raise AttributeError("'bool' object has no attribute 'sum'")  # (None == l+1).sum(), unet3D.py:870
-        outs = feam.run_feam3(self, input, renew=(mask, self.num_classes, self.alpha))
-        return outs[0], outs[1], outs[2]
+        tokens = [self.class_token1, self.class_token2, self.class_token3]
+        outs = feam.run_feam3(self, input, self._levels(tokens, (mask, self.num_classes, self.alpha)))
+        return outs[:3] if self.training else outs
 
 
 class unet3D_with_deepsup(_TrunkMixin, nn.Module):
@@ -362,47 +341,13 @@ class unet3D_with_deepsup(_TrunkMixin, nn.Module):
         self.num_classes = num_classes
         self.use_cm = use_cm
         super().__init__()
-        _build_deep_trunk(self, layers, num_classes, eam=False)
-        self._u3d_cfg = trunk.TrunkCfg(layers=tuple(layers), weight_std=bool(self.weight_std))
-        if ema:
-            for param in self.parameters():
-                param.detach_()
+        self._build_trunk(1, 32, layers, 16, 16, 16, num_classes, deep=True)
+        self._ema_detach(ema)
 
     def forward(self, input, ids=None):
         from u3d import feam
-        outs = feam.run_feam3(self, input, eam=False)
-        if self.training:
-            return outs[0], outs[2]
-        return outs
-
-
-def _build_eam_trunk(self, layers, num_classes, eams, linears):
-    """The modules of unet3D_with_eam (:439-475), unet3D_with_eam_baseline (:1377-1412) and unet3D_with_feam
-    (:1201-1235) in the reference's registration order: the trunk with an EAM after x8 / x4 / x2_resb (the first
-    ``eams`` of them) and, after the first ``linears`` EAMs, the Linear that hands the class message down a level."""
-    mk = lambda cin, cout, n, s: _make_layer(self, NoBottleneck, cin, cout, n, stride=s)  # noqa: E731
-    self.conv1 = conv3x3x3(1, 32, stride=[1, 1, 1], weight_std=self.weight_std)
-    self.layer0 = mk(32, 32, layers[0], (1, 1, 1))
-    self.layer1 = mk(32, 64, layers[1], (2, 2, 2))
-    self.layer2 = mk(64, 128, layers[2], (2, 2, 2))
-    self.layer3 = mk(128, 256, layers[3], (2, 2, 2))
-    self.layer4 = mk(256, 256, layers[4], (2, 2, 2))
-    self.fusionConv = nn.Sequential(
-        nn.GroupNorm(16, 256), nn.ReLU(inplace=in_place),
-        conv3x3x3(256, 256, kernel_size=(1, 1, 1), padding=(0, 0, 0), weight_std=self.weight_std))
-    self.upsamplex2 = nn.Upsample(scale_factor=2, mode="trilinear")
-    for k, (name, cin, cout, ekey, lkey) in enumerate((("x8_resb", 256, 128, "eam84", "linear84_2_42"),
-                                                       ("x4_resb", 128, 64, "eam42", "linear42_2_21"),
-                                                       ("x2_resb", 64, 32, "eam21", None))):
-        setattr(self, name, mk(cin, cout, 1, (1, 1, 1)))
-        if k < eams:
-            setattr(self, ekey, EAM(cout, input_resolution=None, num_heads=4))
-        if k < linears:
-            setattr(self, lkey, nn.Linear(cout, cout // 2))
-    self.x1_resb = mk(32, 32, 1, (1, 1, 1))
-    self.precls_conv = nn.Sequential(nn.GroupNorm(16, 32), nn.ReLU(inplace=in_place),
-                                     nn.Conv3d(32, num_classes, kernel_size=1))
-    self._u3d_cfg = trunk.TrunkCfg(layers=tuple(layers), weight_std=bool(self.weight_std))
+        outs = feam.run_feam3(self, input, [feam.Level(deep=True)] * 3)
+        return (outs[0], outs[2]) if self.training else outs
 
 
 def _cascade(use_cm, n):
@@ -416,6 +361,7 @@ class unet3D_with_eam(_TrunkMixin, nn.Module):
     Linear and is the next level's token. forward(input, task_id) -> train: (logits, cm [1, num_classes, C of the last
     level run], atten_map); eval: logits (the EAMs are not run). Batch 1, as the reference's EAM reshape demands;
     with use_cm[0] false a train forward fails as the reference's does, on the cm it never made."""
+    EAMS = 3   # eam84 -> linear84_2_42 -> eam42 -> linear42_2_21 -> eam21 (:439-475)
 
     def __init__(self, layers, num_classes=12, weight_std=False, ema=False, use_cm=[True, True, True]):  # noqa: B006
         self.inplanes = 128
@@ -423,11 +369,9 @@ class unet3D_with_eam(_TrunkMixin, nn.Module):
         self.num_classes = num_classes
         self.use_cm = use_cm
         super().__init__()
-        _build_eam_trunk(self, layers, num_classes, eams=3, linears=2)
+        self._build_trunk(1, 32, layers, 16, 16, 16, num_classes, eams=self.EAMS, linears=self.EAMS - 1)
         self.class_token = nn.Parameter(torch.randn(num_classes, 128))
-        if ema:
-            for param in self.parameters():
-                param.detach_()
+        self._ema_detach(ema)
 
     def _gates(self):
         return _cascade(self.use_cm, 3)
@@ -443,14 +387,10 @@ class unet3D_with_eam(_TrunkMixin, nn.Module):
 
 class unet3D_with_eam_baseline(unet3D_with_eam):
     """Reference unet3D.py:1370-1504: two EAM levels (eam84 -> linear84_2_42 -> eam42), always on; cm is eam42's."""
+    EAMS = 2
 
     def __init__(self, layers, num_classes=12, weight_std=False):
-        self.inplanes = 128
-        self.weight_std = weight_std
-        self.num_classes = num_classes
-        nn.Module.__init__(self)
-        _build_eam_trunk(self, layers, num_classes, eams=2, linears=1)
-        self.class_token = nn.Parameter(torch.randn(num_classes, 128))
+        super().__init__(layers, num_classes, weight_std)
 
     def _gates(self):
         return [True, True]
@@ -472,31 +412,30 @@ class unet3D_with_feam(_TrunkMixin, nn.Module):
         self.use_cm = use_cm
         self.deep_up = False
         super().__init__()
-        _build_eam_trunk(self, layers, num_classes, eams=3, linears=0)
+        self._build_trunk(1, 32, layers, 16, 16, 16, num_classes, eams=3)
         self.class_token1 = nn.Parameter(torch.randn(num_classes - 1, 128))
         self.class_token2 = nn.Parameter(torch.randn(num_classes - 1, 64))
         self.class_token3 = nn.Parameter(torch.randn(num_classes - 1, 32))
-        if ema:
-            for param in self.parameters():
-                param.detach_()
+        self._ema_detach(ema)
 
     def forward(self, input, mask=None):
         from u3d import feam
-        gates = _cascade(self.use_cm, 3)
         feam.ops.require_device(input)
-        if not self.training:
-            return feam.run_feam3(self, input, deep_heads=False, gates=gates)
-        if mask is None:
-            raise AttributeError("'bool' object has no attribute 'sum'")  # (None == l+1).sum(), unet3D.py:1302
-        feam.ops.require_device(mask)
-        renew = (mask, self.RENEW_CLASSES, self.ALPHA)
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            sizes = [tuple(s // f for s in input.shape[2:]) for f in (8, 4, 2)]
-            if feam.labels_reach(mask, sizes, self.RENEW_CLASSES):
-                raise RuntimeError("a leaf Variable that requires grad is being used in an in-place operation.")
-            renew = None   # no label reaches a level: the renewal writes nothing
-        outs = feam.run_feam3(self, input, renew=renew, deep_heads=False, gates=gates)
-        return outs[0], outs[1]
+        renew = None
+        if self.training:
+            if mask is None:
+                raise AttributeError("'bool' object has no attribute 'sum'")  # (None == l+1).sum(), unet3D.py:1302
+            feam.ops.require_device(mask)
+            renew = (mask, self.RENEW_CLASSES, self.ALPHA)
+            if trunk.wants_grad(self.parameters()):
+                sizes = [tuple(s // f for s in input.shape[2:]) for f in (8, 4, 2)]
+                if feam.labels_reach(mask, sizes, self.RENEW_CLASSES):
+                    raise RuntimeError("a leaf Variable that requires grad is being used in an in-place operation.")
+                renew = None   # no label reaches a level: the renewal writes nothing
+        tokens = [self.class_token1, self.class_token2, self.class_token3]
+        levels = [feam.Level(renew=renew, token=t, attend=g) for t, g in zip(tokens, _cascade(self.use_cm, 3))]
+        outs = feam.run_feam3(self, input, levels)
+        return outs[:2] if self.training else outs
 
 
 # get_style_discriminator (a (2, 3, 2) conv) is not built by the driver: SURVEY.md §2, out of scope.

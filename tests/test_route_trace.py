@@ -4,7 +4,10 @@ slot and size, nothing launched) and route_trace_expected.json holds a digest of
 by ``tools/route_trace.py --write`` from the tree before the routing was gathered into ops.conv_route, so a routing
 change shows here as a changed digest (``--dump DIR`` on both trees, then diff, names the call). The configurations
 that steer a conv's backward on the tape (backward flags, tape pieces, a formed loss gradient) were added with
-ops.conv_bwd; their digests were written from the u3d package of the commit before it."""
+ops.conv_bwd; their digests were written from the u3d package of the commit before it. The
+whole-model configurations (model/...: model.forward and torch.autograd.backward of every model class, through the
+autograd Function) were written from the tree before the model layer was gathered into trunk.TapeFn / trunk.run_model
+(DESIGN.md section 22)."""
 import json
 import os
 import sys
@@ -34,6 +37,12 @@ def test_recorded_configurations_are_the_expected_ones():
         assert {f"trunk/{m}/{i}" for i in rt.TRUNK_INPUTS} <= names
         assert {f"trunk/{m}/bf16_2x96/{f}" for f in rt.FLAG_SETS} <= names
     assert WANT["trunk/unet3D/bf16_2x96"]["calls"]["u3d_conv32_ring_stats"] > 0  # the flagship step runs the ring
+    assert len(rt.MODEL_TAGS) == 8
+    for tag in rt.MODEL_TAGS:  # every model class through model.forward and autograd, and one inference each
+        assert {f"model/{tag}/{i}" for i in rt.MODEL_INPUTS} | {f"model/{tag}/bf16_1x32/inference"} <= names
+    for tag, entry in (("unet3D", "u3d_dynhead_bwd"), ("feam3_up", "u3d_upsample_trilinear_bwd"),
+                       ("feam2_ema", "u3d_renew_token"), ("eam", "u3d_eam_pool_bwd"), ("feam", "u3d_eam_param_bwd")):
+        assert WANT[f"model/{tag}/fp32_1x32"]["calls"][entry] > 0  # (the step ran whole: an error would end it early)
 
 
 @pytest.mark.parametrize("name", sorted(WANT))

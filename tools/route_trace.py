@@ -151,6 +151,51 @@ TRUNK_INPUTS = {
 MODELS = ("unet3D", "baseline", "unet3D_g")
 
 
+# ------------------------------------------------------------------------------------------ whole model steps
+L5 = [1, 2, 2, 2, 2]
+MODEL_TAGS = {   # tag -> (constructor on the unet3D module, what forward takes after the input volume)
+    "unet3D": (lambda u: u.unet3D(L5, 16, True), "task"),
+    "feam3": (lambda u: u.unet3D_with_feam3(L5, 16, True, deep_up=False), None),
+    "feam3_up": (lambda u: u.unet3D_with_feam3(L5, 16, True, deep_up=True), None),
+    "feam2_ema": (lambda u: u.unet3D_with_feam2(L5, 16, True, ema=True), "mask"),  # (train mode renews the tokens)
+    "deepsup": (lambda u: u.unet3D_with_deepsup(L5, 16, True), None),
+    "eam": (lambda u: u.unet3D_with_eam(L5, 16, True), None),
+    "eam_baseline": (lambda u: u.unet3D_with_eam_baseline(L5, 16, True), None),
+    "feam": (lambda u: u.unet3D_with_feam(L5, 16, True), "no_label"),
+}
+MODEL_INPUTS = ("bf16_1x32", "fp32_1x32")
+
+
+def _flat(outs):
+    if torch.is_tensor(outs):
+        return [outs]
+    return [t for o in outs if o is not None for t in _flat(o)]
+
+
+def model_step(tag, shape, dtype, train=True):
+    """model.forward of a whole model class on a meta input [n, d, h, w], through the autograd Function, and (train)
+    torch.autograd.backward with a gradient on every differentiable output. The pack cache is off: its test asks
+    torch about stream capture, which needs a device."""
+    import unet3D
+    make, extra = MODEL_TAGS[tag]
+    with torch.device("meta"):
+        m = make(unet3D)
+    m.compute_dtype = dtype
+    m.train(train)
+    n, d, h, w = shape
+    args = [meta((n, 1, d, h, w))]
+    if extra == "task":
+        args.append(meta((n,), torch.int64))
+    elif extra == "mask":
+        args.append(meta((n, 1, d, h, w)))
+    elif extra == "no_label":  # read on the host (feam.labels_reach): a real tensor, all background
+        args.append(torch.zeros((n, 1, d, h, w)))
+    with flags(PACK_CACHE_OK=[False]), torch.set_grad_enabled(train):
+        outs = [t for t in _flat(m(*args)) if t.requires_grad]
+        if outs:
+            torch.autograd.backward(outs, [meta(t.shape, t.dtype) for t in outs])
+
+
 # ------------------------------------------------------------------------------------------ tape pieces
 def _conv_params(P, key, cin, cout, k, gn_key=None, bias=False):
     P[key + ".weight"] = meta((cout, cin, k, k, k))
@@ -187,7 +232,7 @@ def _lone_conv(c):  # no GroupNorm in front: unet3D.Conv3d on its own (subgraph)
     return build
 
 
-def _deep_head(cin):  # feam._feam3_forward's deepout heads; cin 32 / 64 run the streaming head, 128 the implicit GEMM
+def _deep_head(cin):  # a feam.Level's deep head (feam._feam3_forward); cin 32 / 64 run the streaming head, 128 the implicit GEMM
     def build(P):
         _conv_params(P, "deepout.2", cin, 16, 1, "deepout.0", bias=True)
         return lambda tape, x: tape.gn_conv(x, "deepout.2", 1, 1, gn_key="deepout.0", G=16, bias=True, out_f32=True,
@@ -296,6 +341,11 @@ def configs():
         out[f"trunk/{m}/bf16_2x96/inference"] = lambda t, m=m: trunk_step(m, (2, 96, 96, 96), torch.bfloat16, False)
     out["trunk/baseline/bf16_2x96/plain_grad"] = lambda t: trunk_step("baseline", (2, 96, 96, 96), torch.bfloat16,
                                                                       plain_grad=True)
+    for tag in MODEL_TAGS:
+        for iname in MODEL_INPUTS:
+            shape, dtype = TRUNK_INPUTS[iname]
+            out[f"model/{tag}/{iname}"] = lambda t, g=tag, s=shape, dt=dtype: model_step(g, s, dt)
+        out[f"model/{tag}/bf16_1x32/inference"] = lambda t, g=tag: model_step(g, (1, 32, 32, 32), torch.bfloat16, False)
     for pname, (build, cin, gdtype) in TAPE_PIECES.items():
         for e in TAPE_EDGES:
             out[f"tape/{pname}/{e}"] = lambda t, b=build, c=cin, e=e, g=gdtype: tape_piece(b, c, e, g)
