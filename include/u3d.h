@@ -493,6 +493,36 @@ int u3d_deepsup_loss_bwd(int L, const float* const* logits, const int* dims, con
                          const float* target, int S, int D, int H, int W, int C, const float* weights,
                          const double* sums, const float* grad_out, float* const* dlogits, u3d_stream_t stream);
 
+/* ---------------------------------------------------------------- per-sample supervision (additive)
+ * The two losses above with one supervision row per sample: weights fp32 [S][C], any values; sample s supervises
+ * class c when weights[s][c] != 0. With n_c = the number of supervising samples and w^_c = sum_s w_sc / n_c (0 when
+ * n_c = 0), the per-sample sums are pooled over the supervising samples only (fp64, s ascending) and
+ *   loss = sum_c w^_c d_c / C + [uce] sum_{c: n_c > 0} w^_c B_c / (n_c V),  d_c = 1 - (2 I_c + 1e-5) / (Z_c + Y_c + 1e-5).
+ * Equal rows give the batch loss above with that row; a sample whose row is all zero gets a gradient of exactly 0
+ * and enters no sum; all rows zero give loss 0. uce: 0 or 1 (the cross entropy of uce 2 is unweighted: U3D_EINVAL).
+ * sums_ps fp64 [S][C][4] = per sample and class (sum p*t, sum p^2, sum t, sum BCE), unmasked; pooled fp64 [C][5] =
+ * (I, Z, Y, B, n_c); loss fp32 [1]. ws: u3d_loss_ps_workspace_bytes(S, V, C) bytes. S <= 65535. */
+long long u3d_loss_ps_workspace_bytes(int S, long long V, int C);
+int u3d_partial_loss_ps_fwd(const float* logits, const float* labels, int S, long long V, int C, int softmax,
+                            const float* weights, int uce, double* sums_ps, double* pooled, float* loss, float* ws,
+                            u3d_stream_t stream);
+/* dlogits (dtype_out, [S][V][C]) = d loss / d logits * grad_out[0] (device scalar), from the forward's pooled sums */
+int u3d_partial_loss_ps_bwd(int dtype_out, const float* logits, const float* labels, int S, long long V, int C,
+                            int softmax, const float* weights, int uce, const double* pooled, const float* grad_out,
+                            void* dlogits, u3d_stream_t stream);
+/* u3d_deepsup_loss_fwd / _bwd with weights fp32 [S][C]: per level the pooling rule above with uce 0, the nearest
+ * label map and the level weights unchanged. sums_ps fp64 [L][S][C][4] (the last entry 0), pooled fp64 [L][C][5]
+ * (I, Z, Y, 0, n_c), level_loss fp32 [L], loss fp32 [1]. ws: u3d_deepsup_loss_ps_workspace_bytes(L, C, S) bytes.
+ * Fewer than 2^26 voxels per level and sample, S <= 65535. */
+long long u3d_deepsup_loss_ps_workspace_bytes(int L, int C, int S);
+int u3d_deepsup_loss_ps_fwd(int L, const float* const* logits, const int* dims, const float* level_weights,
+                            const float* target, int S, int D, int H, int W, int C, const float* weights,
+                            double* sums_ps, double* pooled, float* level_loss, float* loss, float* ws,
+                            u3d_stream_t stream);
+int u3d_deepsup_loss_ps_bwd(int L, const float* const* logits, const int* dims, const float* level_weights,
+                            const float* target, int S, int D, int H, int W, int C, const float* weights,
+                            const double* pooled, const float* grad_out, float* const* dlogits, u3d_stream_t stream);
+
 /* Partial-label target (A12, train_amos_atlas_final.py:252-255): out = labels with every label l in [lmin, lmax]
  * whose mask[s][l] == 0 set to 0; mask int64 [S][mask_stride] (mask_stride 0 = one vector for the batch), length M. */
 int u3d_partial_target(const float* labels, int S, long long V, const long long* mask, int mask_stride, int M,

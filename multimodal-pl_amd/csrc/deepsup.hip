@@ -277,3 +277,240 @@ extern "C" int u3d_deepsup_loss_bwd(int L, const float* const* logits, const int
 #undef LAUNCH
   return check_launch("deepsup_loss_bwd");
 }
+
+// ------------------------------------------------------------------------------------ per-sample supervision
+// The same loss with one supervision row per sample (weights [S][C], the pooling rule of loss_ps.hip with uce 0, per
+// level): sample s enters level l's sums of class c only when w[s][c] != 0. The grid is 2-D, the sample on blockIdx.y;
+// the block prefix table counts one sample's blocks (ds_fill with S = 1) and the labels are read through the same
+// nearest map from the sample's own target volume. Forward: per-(sample, block) partials to fixed workspace slots, a
+// combine launch (fp64, fixed order) to sums_ps [L][S][C][4], a one-workgroup launch that pools them over the
+// supervising samples in ascending s (pooled [L][C][5] = I, Z, Y, 0, n_c) and forms the level losses and the loss.
+namespace u3d {
+
+constexpr int DS_PS_MAXS = 65535;  // gridDim.y
+
+template <int NC>
+__global__ __launch_bounds__(DT) void deepsup_ps_fwd_kernel(DsArgs g, const float* __restrict__ tgt, int D, int H,
+                                                           int W, int C, float* __restrict__ ws) {
+  __shared__ float red[DT / 64][3 * NC];
+  const DsLevel lv = ds_level(g, blockIdx.x);
+  const int smp = blockIdx.y;
+  float acc[3][NC];
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+#pragma unroll
+    for (int c = 0; c < NC; ++c) acc[k][c] = 0.f;
+  const unsigned nvox = (unsigned)lv.d * lv.h * lv.w, stride = (unsigned)lv.nb * DT;  // one sample's, < 2^31 / 32
+  const float* lg = lv.lg + (long long)smp * nvox * C;
+  const float* st = tgt + (long long)smp * D * H * W;
+  for (unsigned v = (blockIdx.x - lv.b0) * DT + threadIdx.x; v < nvox; v += stride) {
+    const float t = ds_label(lv, v, st, D, H, W);
+    float x[NC], e[NC], s, inv;
+    softmax_fast<NC>(lg + (long long)v * C, C, x, e, s, inv);
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+      if (c < C) {
+        const float tc = (t == (float)c) ? 1.f : 0.f, p = e[c] * inv;
+        acc[0][c] = fmaf(p, tc, acc[0][c]);
+        acc[1][c] = fmaf(p, p, acc[1][c]);
+        acc[2][c] += tc;
+      }
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+      if (c < C) {
+        const float s = wave_sum(acc[k][c]);
+        if (lane == 0) red[wave][k * NC + c] = s;
+      }
+  __syncthreads();
+  float* out = ws + ((long long)smp * gridDim.x + blockIdx.x) * 3 * C;
+  for (int i = threadIdx.x; i < 3 * C; i += DT) {
+    const int k = i / C, c = i % C;
+    float s = 0.f;
+    for (int w = 0; w < DT / 64; ++w) s += red[w][k * NC + c];
+    out[i] = s;
+  }
+}
+
+// block (l, s): sums_ps[l][s][c][0..2] = the sample's per-block partials of the level added in fp64 (a wave per
+// (sum, class), lanes over the blocks in order, then the xor tree: fixed order), [3] = 0
+__global__ __launch_bounds__(DT) void deepsup_ps_combine_kernel(DsArgs g, int C, int S, const float* __restrict__ ws,
+                                                               double* __restrict__ sums_ps) {
+  const int l = blockIdx.x, smp = blockIdx.y;
+  int b0 = g.blk[0], b1 = g.blk[1];
+#pragma unroll
+  for (int k = 1; k < DS_MAXL; ++k)
+    if (k == l) {
+      b0 = g.blk[k];
+      b1 = g.blk[k + 1];
+    }
+  const float* src = ws + (long long)smp * g.blk[DS_MAXL] * 3 * C;
+  double* out = sums_ps + ((long long)l * S + smp) * C * 4;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int i = wave; i < 3 * C; i += DT / 64) {
+    double a = 0;
+    for (int b = b0 + lane; b < b1; b += 64) a += src[(long long)b * 3 * C + i];
+    a = wave_sum(a);
+    if (lane == 0) out[(i % C) * 4 + i / C] = a;
+  }
+  for (int c = threadIdx.x; c < C; c += DT) out[c * 4 + 3] = 0;
+}
+
+// One workgroup: pooled[l][c] over the supervising samples (s ascending, fp64), level_loss[l] as deepsup_final_kernel
+// forms it with w^_c (loss_grad.h), loss = sum_l weight_l * level_loss_l in fp32 in level order.
+__global__ __launch_bounds__(DT) void deepsup_ps_final_kernel(DsArgs g, int C, int S, const float* __restrict__ w,
+                                                             const double* __restrict__ sums_ps,
+                                                             double* __restrict__ pooled,
+                                                             float* __restrict__ level_loss, float* __restrict__ loss) {
+  __shared__ double sd[DS_MAXL][DS_CMAX];
+  __shared__ float slw[DS_MAXL], sll[DS_MAXL];
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < DS_MAXL; ++k) slw[k] = g.lw[k];
+  }
+  const int L = g.L;
+  for (int i = threadIdx.x; i < L * C; i += DT) {
+    const int l = i / C, c = i % C;
+    double X[3] = {0, 0, 0}, n = 0;
+    for (int s = 0; s < S; ++s)
+      if (w[(long long)s * C + c] != 0.f) {
+        const double* q = sums_ps + (((long long)l * S + s) * C + c) * 4;
+        X[0] += q[0];
+        X[1] += q[1];
+        X[2] += q[2];
+        n += 1;
+      }
+    double* o = pooled + (long long)i * 5;
+    o[0] = X[0];
+    o[1] = X[1];
+    o[2] = X[2];
+    o[3] = 0;
+    o[4] = n;
+    const float d = 1.f - (float)((2.0 * X[0] + 1e-5) / (X[1] + X[2] + 1e-5));
+    sd[l][c] = (double)d * ps_class_weight(c, S, C, w, n);
+  }
+  __syncthreads();
+  if (threadIdx.x < L) {
+    const int l = threadIdx.x;
+    double dice = 0;
+    for (int c = 0; c < C; ++c) dice += sd[l][c];
+    const float ll = (float)(dice / C);
+    level_loss[l] = ll;
+    sll[l] = ll;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float t = 0.f;
+    for (int l = 0; l < L; ++l) t += sll[l] * slw[l];
+    loss[0] = t;
+  }
+}
+
+template <int NC>
+__global__ __launch_bounds__(DT) void deepsup_ps_bwd_kernel(DsArgs g, const float* __restrict__ tgt, int S, int D,
+                                                           int H, int W, int C, const float* __restrict__ w,
+                                                           const double* __restrict__ pooled,
+                                                           const float* __restrict__ gout) {
+  __shared__ float kd_a[NC], kd_b[NC];
+  const DsLevel lv = ds_level(g, blockIdx.x);
+  const int smp = blockIdx.y;
+  int sup = 0;
+  if (threadIdx.x < NC) {
+    const int c = threadIdx.x;
+    float a, b, e;
+    dice_bce_coefs_ps(c, smp, S, C, pooled + (long long)lv.l * C * 5, w, gout, 0, 1.0, a, b, e);
+    kd_a[c] = a * lv.lw;
+    kd_b[c] = b * lv.lw;
+    sup = c < C && w[(long long)smp * C + c] != 0.f;
+  }
+  const int any = __syncthreads_or(sup);
+  const unsigned nvox = (unsigned)lv.d * lv.h * lv.w, stride = (unsigned)lv.nb * DT;
+  const float* lg = lv.lg + (long long)smp * nvox * C;
+  float* dl = lv.dl + (long long)smp * nvox * C;
+  if (!any) {  // the sample supervises no class: zeros, without reading the logits
+    const long long total = (long long)nvox * C;
+    for (long long i = (long long)(blockIdx.x - lv.b0) * DT + threadIdx.x; i < total; i += stride) dl[i] = 0.f;
+    return;
+  }
+  const float* st = tgt + (long long)smp * D * H * W;
+  for (unsigned v = (blockIdx.x - lv.b0) * DT + threadIdx.x; v < nvox; v += stride) {
+    const float t = ds_label(lv, v, st, D, H, W);
+    float x[NC], p[NC], s, inv;
+    softmax_fast<NC>(lg + (long long)v * C, C, x, p, s, inv);
+    float gr[NC], dot = 0.f;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      p[c] *= inv;
+      gr[c] = 0.f;
+      if (c < C) {
+        const float tc = (t == (float)c) ? 1.f : 0.f;
+        gr[c] = fmaf(tc, kd_a[c], p[c] * kd_b[c]);
+        dot = fmaf(gr[c], p[c], dot);
+      }
+    }
+    float* o = dl + (long long)v * C;
+    if constexpr (NC % 4 == 0 && NC <= 16) {
+#pragma unroll
+      for (int c = 0; c < NC; c += 4)
+        *reinterpret_cast<f32x4*>(o + c) = f32x4{p[c] * (gr[c] - dot), p[c + 1] * (gr[c + 1] - dot),
+                                                 p[c + 2] * (gr[c + 2] - dot), p[c + 3] * (gr[c + 3] - dot)};
+    } else {
+#pragma unroll
+      for (int c = 0; c < NC; ++c)
+        if (c < C) o[c] = p[c] * (gr[c] - dot);
+    }
+  }
+}
+
+}  // namespace u3d
+
+extern "C" long long u3d_deepsup_loss_ps_workspace_bytes(int L, int C, int S) {
+  return (long long)std::max(S, 1) * std::max(L, 1) * DS_FWD_NB * 3 * std::max(C, 1) * 4;
+}
+
+extern "C" int u3d_deepsup_loss_ps_fwd(int L, const float* const* logits, const int* dims, const float* level_weights,
+                                       const float* target, int S, int D, int H, int W, int C, const float* weights,
+                                       double* sums_ps, double* pooled, float* level_loss, float* loss, float* ws,
+                                       u3d_stream_t stream) {
+  U3D_REQUIRE(logits && dims && level_weights && target && weights && sums_ps && pooled && level_loss && loss && ws,
+              "deepsup_loss_ps_fwd: null pointer");
+  U3D_REQUIRE(L >= 1 && L <= DS_MAXL && C >= 1 && C <= DS_CMAX && S >= 1 && D >= 1 && H >= 1 && W >= 1,
+              "deepsup_loss_ps_fwd: L=%d (max %d) C=%d (max %d) S=%d target %dx%dx%d unsupported", L, DS_MAXL, C,
+              DS_CMAX, S, D, H, W);
+  U3D_REQUIRE(S <= DS_PS_MAXS, "deepsup_loss_ps_fwd: S=%d samples (the grid takes %d at most)", S, DS_PS_MAXS);
+  DsArgs a;
+  U3D_REQUIRE(ds_fill(a, L, logits, nullptr, dims, level_weights, 1, D, H, W, DS_FWD_NB) == 0,
+              "deepsup_loss_ps_fwd: a level has a null pointer, an empty extent or 2^26 voxels or more per sample");
+  hipStream_t s = (hipStream_t)stream;
+#define LAUNCH(NCV) \
+  hipLaunchKernelGGL(deepsup_ps_fwd_kernel<NCV>, dim3(a.blk[L], S), dim3(DT), 0, s, a, target, D, H, W, C, ws)
+  U3D_NC_DISPATCH(C, LAUNCH)
+#undef LAUNCH
+  hipLaunchKernelGGL(deepsup_ps_combine_kernel, dim3(L, S), dim3(DT), 0, s, a, C, S, ws, sums_ps);
+  hipLaunchKernelGGL(deepsup_ps_final_kernel, dim3(1), dim3(DT), 0, s, a, C, S, weights, sums_ps, pooled, level_loss,
+                     loss);
+  return check_launch("deepsup_loss_ps_fwd");
+}
+
+extern "C" int u3d_deepsup_loss_ps_bwd(int L, const float* const* logits, const int* dims, const float* level_weights,
+                                       const float* target, int S, int D, int H, int W, int C, const float* weights,
+                                       const double* pooled, const float* grad_out, float* const* dlogits,
+                                       u3d_stream_t stream) {
+  U3D_REQUIRE(logits && dims && level_weights && target && weights && pooled && grad_out && dlogits,
+              "deepsup_loss_ps_bwd: null pointer");
+  U3D_REQUIRE(L >= 1 && L <= DS_MAXL && C >= 1 && C <= DS_CMAX && S >= 1 && D >= 1 && H >= 1 && W >= 1,
+              "deepsup_loss_ps_bwd: L=%d C=%d S=%d target %dx%dx%d unsupported", L, C, S, D, H, W);
+  U3D_REQUIRE(S <= DS_PS_MAXS, "deepsup_loss_ps_bwd: S=%d samples (the grid takes %d at most)", S, DS_PS_MAXS);
+  DsArgs a;
+  U3D_REQUIRE(ds_fill(a, L, logits, dlogits, dims, level_weights, 1, D, H, W, DS_BWD_NB) == 0,
+              "deepsup_loss_ps_bwd: a level has a null pointer, an empty extent or 2^26 voxels or more per sample");
+#define LAUNCH(NCV)                                                                                               \
+  hipLaunchKernelGGL(deepsup_ps_bwd_kernel<NCV>, dim3(a.blk[L], S), dim3(DT), 0, (hipStream_t)stream, a, target, S, \
+                     D, H, W, C, weights, pooled, grad_out)
+  U3D_NC_DISPATCH(C, LAUNCH)
+#undef LAUNCH
+  return check_launch("deepsup_loss_ps_bwd");
+}

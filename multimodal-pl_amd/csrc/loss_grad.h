@@ -66,6 +66,37 @@ __device__ __forceinline__ void dice_bce_coefs(int c, int C, const double* __res
   }
 }
 
+// Per-sample supervision (loss_ps.hip, the _ps kernels of deepsup.hip). w [S][C]: sample s supervises class c when
+// w[s][c] != 0; pooled[c] = (I, Z, Y, B, n_c) = the per-sample sums added over the n_c supervising samples.
+// ps_class_weight: w^_c = sum_s w[s][c] / n_c in fp64, s ascending (0 when nobody supervises the class): the one
+// definition the forward's final kernel and every backward block use, so both see the same bits.
+__device__ __forceinline__ double ps_class_weight(int c, int S, int C, const float* __restrict__ w, double n) {
+  double sw = 0;
+  for (int s = 0; s < S; ++s) sw += (double)w[(long long)s * C + c];
+  return n > 0 ? sw / n : 0.0;
+}
+
+// dice_bce_coefs for sample s: a, b from the pooled sums with w^_c, e = w^_c / (n_c V) * g (uce 1: the BCE mean runs
+// over the supervising samples' voxels only); all three 0 where the sample does not supervise the class. Every load
+// is issued before the sample's own weight is looked at (one memory latency per block, not two: a backward block
+// covers few voxels, and its prologue is on its critical path).
+__device__ __forceinline__ void dice_bce_coefs_ps(int c, int s, int S, int C, const double* __restrict__ pooled,
+                                                  const float* __restrict__ w, const float* __restrict__ gout, int uce,
+                                                  double V, float& a, float& b, float& e) {
+  a = b = e = 0.f;
+  if (c < C) {
+    const float wsc = w[(long long)s * C + c], g = gout[0];
+    const double I = pooled[c * 5], Z = pooled[c * 5 + 1], Y = pooled[c * 5 + 2], n = pooled[c * 5 + 4];
+    const double wh = ps_class_weight(c, S, C, w, n);
+    const double num = 2.0 * I + 1e-5, den = Z + Y + 1e-5;
+    const double scale = wh / C * g;
+    const bool sup = wsc != 0.f;  // then n >= 1
+    a = sup ? (float)(-2.0 / den * scale) : 0.f;
+    b = sup ? (float)(2.0 * num / (den * den) * scale) : 0.f;
+    e = sup && uce == 1 ? (float)(wh / (n * V) * g) : 0.f;
+  }
+}
+
 // dL/dlogits of one voxel, 16 classes, softmax + per-class BCE (uce 1): the logits in x4 (4 x 16 B), its label t,
 // the coefficient tables (LDS) -> r[16]. Softmax on the hardware exp2 / rcp (~1 ulp), as the forward. The sums over
 // the classes run as two halves (classes 0-7, 8-15) added at the end — the order dice_bce_softmax_grad8 reproduces

@@ -92,14 +92,15 @@ class Engine(object):
         return torch.mean(tensor)
 
     # ---------------------------------------------------------------------------------------- additive
-    def train_step(self, model, optimizer, images, labels, sup_mask):
+    def train_step(self, model, optimizer, images, labels, sup_mask, per_sample=False):
         """One pre-train step as train_amos_atlas_final.py:258-378 runs it for the trunk: forward, partial
-        Dice+BCE (get_loss pre-train branch), backward (gradient all-reduce inside), SGD step."""
+        Dice+BCE (get_loss pre-train branch), backward (gradient all-reduce inside), SGD step.
+        per_sample: ``sup_mask`` holds one row per sample of the batch (a list of S rows or a [S, >= C] tensor)."""
         from loss_functions.losses import get_loss
         optimizer.zero_grad(set_to_none=True)
         out = model(images, labels)
         preds = out[0] if isinstance(out, (tuple, list)) else out
-        loss, _ = get_loss(preds, 0, [], labels, [sup_mask])
+        loss, _ = get_loss(preds, 0, [], labels, sup_mask if per_sample else [sup_mask], per_sample=per_sample)
         loss.backward()
         optimizer.step()
         return loss

@@ -25,28 +25,38 @@ class DiceLoss(nn.Module):
     def _one_hot_encoder(self, input_tensor):
         return torch.cat([(input_tensor == i).unsqueeze(1) for i in range(self.n_classes)], dim=1).float()
 
-    def forward(self, inputs, target, weight=None, softmax=True, mask=None):
+    def forward(self, inputs, target, weight=None, softmax=True, mask=None, per_sample=False):
+        """per_sample (additive): ``weight`` is [S, C], one row per sample (u3d.loss.sample_weights)."""
         if mask is not None:
             raise NotImplementedError("DiceLoss spatial mask argument is not on the native path")
         assert inputs.shape[1] == self.n_classes, "predict & target shape do not match"
-        w = _L.class_weights(None if weight is None else [weight], self.n_classes, inputs.device)
+        if per_sample:
+            w = _L.sample_weights(weight, inputs.shape[0], self.n_classes, inputs.device)
+        else:
+            w = _L.class_weights(None if weight is None else [weight], self.n_classes, inputs.device)
         return _L.partial_loss(inputs, target, w, mode=_L.MODE_IDENTITY, uce=False)
 
 
 class EDiceLoss_partial(nn.Module):
-    """Reference loss_partial.py:59-99."""
+    """Reference loss_partial.py:59-99. ``per_sample=True`` (additive, off by default): ``mask`` holds one row per
+    sample and each sample enters a class's Dice and BCE sums only where its own row supervises that class
+    (u3d.loss.sample_weights, DESIGN.md "Per-sample supervision"); the default is the reference's mask[0]."""
 
-    def __init__(self, n_classes):
+    def __init__(self, n_classes, per_sample=False):
         super().__init__()
         self.labels = ["ET", "TC", "WT"] + ["a"] * 20
         self.device = "cpu"
         self.n_classes = n_classes
+        self.per_sample = bool(per_sample)
         self.diceloss = DiceLoss(n_classes=n_classes)
         self.bce = nn.BCELoss()
 
     def forward(self, inputs, target, mask=None, soft_max=True, uce=True):
         C = inputs.shape[1]
-        w = _L.class_weights(mask, C, inputs.device)
+        if self.per_sample:
+            w = _L.sample_weights(mask, inputs.shape[0], C, inputs.device)
+        else:
+            w = _L.class_weights(mask, C, inputs.device)
         mode = _L.MODE_SOFTMAX if soft_max else _L.MODE_SIGMOID
         return _L.partial_loss(inputs, target, w, mode=mode, uce=bool(uce))
 

@@ -9,7 +9,7 @@ from loss_functions.loss_partial import EDiceLoss_full, EDiceLoss_partial
 
 
 def get_loss(output, cm, deep_out, target, mask=None, catlas=None, attns=None, refine_output=None, label_t=None,
-             discard=0.05, confi_=0.10, aux_weight=1, weight_feature=0.1):
+             discard=0.05, confi_=0.10, aux_weight=1, weight_feature=0.1, per_sample=False):
     """EDiceLoss_partial(C)(output, target.squeeze(1), soft_max=True, mask=mask); with ``refine_output`` plus the
     consistency term: masked soft Dice of every attention map (sigmoid) and of softmax(output)[:, 1:] against the
     refiner's confident foreground for the organs label_t marks unsupervised (u3d.loss.consistency_aux, one fused
@@ -21,12 +21,16 @@ def get_loss(output, cm, deep_out, target, mask=None, catlas=None, attns=None, r
     (u3d.loss.deep_supervision_loss, one fused pass over all levels). As in the reference the term joins the
     consistency branch only: the pre-train branch returns ``dice_loss`` and drops it (:179-182), so the deep maps get
     no gradient there and nothing is computed for them. More than four levels raise IndexError, a level with another
-    class count or batch AssertionError. The per-level ``.detach().cpu()`` (:127) is dropped (no host sync)."""
+    class count or batch AssertionError. The per-level ``.detach().cpu()`` (:127) is dropped (no host sync).
+
+    ``per_sample`` (additive, off by default): ``mask`` holds one supervision row per sample instead of the
+    reference's mask[0] for the whole batch; it reaches the main term and the ``deep_out`` term. The consistency
+    term keeps its batch-1 ``label_t``."""
     from u3d import loss as L
     deep_out = list(deep_out)
     if deep_out:
         L.check_deep_levels(deep_out, target, output.shape[1])
-    edice = EDiceLoss_partial(output.shape[1])
+    edice = EDiceLoss_partial(output.shape[1], per_sample=per_sample)
     dice_loss = edice(output, target.squeeze(1), soft_max=True, mask=mask)
     if refine_output is None:
         return dice_loss, confi_
@@ -34,7 +38,7 @@ def get_loss(output, cm, deep_out, target, mask=None, catlas=None, attns=None, r
         label_t = torch.tensor(label_t, dtype=torch.float32)
     aux = L.consistency_aux(output, list(attns), refine_output, label_t, weight_feature, confi=0.10)
     if deep_out:
-        aux = L.deep_supervision_loss(deep_out, target, mask) + aux
+        aux = L.deep_supervision_loss(deep_out, target, mask, per_sample=per_sample) + aux
     return dice_loss + aux * aux_weight, 0.10
 
 

@@ -108,6 +108,12 @@ _SIGS = {
     "u3d_deepsup_loss_workspace_bytes": [I, I],
     "u3d_deepsup_loss_fwd": [I, P, P, P, P, I, I, I, I, I, P, P, P, P, P, P],
     "u3d_deepsup_loss_bwd": [I, P, P, P, P, I, I, I, I, I, P, P, P, P, P],
+    "u3d_loss_ps_workspace_bytes": [I, L, I],
+    "u3d_partial_loss_ps_fwd": [P, P, I, L, I, I, P, I, P, P, P, P, P],
+    "u3d_partial_loss_ps_bwd": [I, P, P, I, L, I, I, P, I, P, P, P, P],
+    "u3d_deepsup_loss_ps_workspace_bytes": [I, I, I],
+    "u3d_deepsup_loss_ps_fwd": [I, P, P, P, P, I, I, I, I, I, P, P, P, P, P, P, P],
+    "u3d_deepsup_loss_ps_bwd": [I, P, P, P, P, I, I, I, I, I, P, P, P, P, P],
     "u3d_dice_metric": [P, P, I, L, I, I, P, P, P, P],
     "u3d_dice_metric_binary": [P, I, L, L, L, L, P, P, P, P, P],
     "u3d_gn_relu_mean": [I, P, I, I, L, I, P, P, P, P, P],
@@ -168,7 +174,8 @@ _SIGS = {
 _RESTYPE = {"u3d_stem_fwd_ws_bytes": L, "u3d_stem1_stats_ws_floats": L, "u3d_conv_small_cnt_bytes": L, "u3d_conv_small_spart_floats": L, "u3d_conv_small_gb_parts_floats": L, "u3d_conv_s2_ring_ws_floats": L, "u3d_upsample2x_stats_ws_floats": L, "u3d_wstd_bwd_scratch_bytes": L, "u3d_gn_workspace_bytes": L, "u3d_channel_sum_workspace_bytes": L, "u3d_loss_workspace_bytes": L,
             "u3d_eam_attn_bwd_part_floats": L, "u3d_eam_pool_part_floats": L,"u3d_upsample_trilinear_bwd_ws_floats": L, "u3d_renew_token_ws_bytes": L,
             "u3d_consistency_ws_bytes": L, "u3d_volume_stats_ws_bytes": L, "u3d_convg_brick_stats_ws_floats": L,
-            "u3d_deepsup_loss_workspace_bytes": L, "u3d_disc_conv_fwd_ws_bytes": L, "u3d_disc_conv_wgrad_ws_bytes": L,
+            "u3d_deepsup_loss_workspace_bytes": L, "u3d_loss_ps_workspace_bytes": L,
+            "u3d_deepsup_loss_ps_workspace_bytes": L, "u3d_disc_conv_fwd_ws_bytes": L, "u3d_disc_conv_wgrad_ws_bytes": L,
             "u3d_disc_bias_grad_ws_bytes": L, "u3d_disc_first_wgrad_ws_bytes": L, "u3d_disc_side_wgrad_ws_bytes": L}
 
 _lib = None

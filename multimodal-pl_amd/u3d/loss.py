@@ -28,6 +28,35 @@ def class_weights(mask, C, device):
     return w.reshape(-1)[:C].to(device=device, dtype=torch.float32)
 
 
+def sample_weights(mask, S, C, device):
+    """One supervision row per sample: [S, C] fp32 for the per-sample losses (DESIGN.md "Per-sample supervision").
+    mask: a list of S rows (lists or tensors) or a tensor [S, >= C]; None = all ones. A tensor that already lives on
+    the device is sliced and cast there without a host read, so a captured step can feed it from a static tensor.
+    A row count other than S is a ValueError, rows shorter than C an IndexError (as class_weights)."""
+    if mask is None:
+        return torch.ones((S, C), dtype=torch.float32, device=device)
+    if torch.is_tensor(mask):
+        if mask.dim() != 2:
+            raise ValueError(f"sample_weights: a [S, >= C] tensor or a list of S rows expected, got {tuple(mask.shape)}")
+        rows = mask
+    else:
+        rows = list(mask)
+        if len(rows) != S:
+            raise ValueError(f"sample_weights: {len(rows)} mask rows for a batch of {S}")
+        rows = [r if torch.is_tensor(r) else torch.tensor(r) for r in rows]
+        for r in rows:
+            if r.numel() < C:
+                raise IndexError(f"index {r.numel()} is out of bounds for dimension 0 with size {r.numel()} "
+                                 f"(a mask row shorter than the {C} classes)")
+        rows = torch.stack([r.reshape(-1)[:C].to(device=device, dtype=torch.float32) for r in rows])
+    if rows.shape[0] != S:
+        raise ValueError(f"sample_weights: {rows.shape[0]} mask rows for a batch of {S}")
+    if rows.shape[1] < C:
+        raise IndexError(f"index {rows.shape[1]} is out of bounds for dimension 1 with size {rows.shape[1]} "
+                         f"(mask rows shorter than the {C} classes)")
+    return rows[:, :C].to(device=device, dtype=torch.float32).contiguous()
+
+
 class DeferredLossGrad(torch.Tensor):
     """The partial loss's gradient w.r.t. the trunk's logits, handed back unformed when the logits came straight from
     the streaming head (trunk.TapeFn tags them): the trunk's backward passes it to the head, whose backward forms the
@@ -91,10 +120,41 @@ class _PartialLossFn(torch.autograd.Function):
         return form(), None, None, None, None
 
 
+class _PartialLossPsFn(torch.autograd.Function):
+    """The partial loss with one supervision row per sample (weights [S, C], ops.partial_loss_ps_fwd/_bwd)."""
+
+    @staticmethod
+    def forward(ctx, logits, target, weights, mode, uce):
+        lg = ndhwc_view(logits.float())
+        lab = target.float().contiguous()
+        loss, _, pooled = ops.partial_loss_ps_fwd(lg, lab, weights, mode, uce)
+        ctx.save_for_backward(lg, lab, weights, pooled)
+        ctx.mode, ctx.uce = mode, uce
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        lg, lab, weights, pooled = ctx.saved_tensors
+        go = g.reshape(1).float().contiguous()
+        # The streaming head's deferred hand-off (DeferredLossGrad, ops.head_loss_bwd) is declined on purpose, even
+        # when the logits carry a _u3d_head_link: the fused head + loss backward forms the batch loss's gradient from
+        # one weight row. The gradient here always comes from the per-sample backward kernel; porting the hand-off
+        # is a performance change of its own.
+        dl = ops.partial_loss_ps_bwd(lg, lab, weights, pooled, go, ctx.mode, ctx.uce)
+        return dl.permute(0, 4, 1, 2, 3), None, None, None, None
+
+
 def partial_loss(logits, target, weights, mode=MODE_SOFTMAX, uce=True):
+    """weights [C]: the batch loss (the reference's mask[0] for every sample). weights [S, C] (sample_weights): the
+    per-sample loss; uce must then be 0 or 1."""
     ops.require_device(logits, target)
     if target.shape[0] != logits.shape[0] or target.numel() * logits.shape[1] != logits.numel():
         raise AssertionError(f"predict {tuple(logits.shape)} & target {tuple(target.shape)} shape do not match")
+    if weights.dim() == 2:
+        if tuple(weights.shape) != (logits.shape[0], logits.shape[1]):
+            raise ValueError(f"partial_loss: per-sample weights {tuple(weights.shape)} for logits "
+                             f"{tuple(logits.shape)}: [S, C] expected")
+        return _PartialLossPsFn.apply(logits, target, weights.float().contiguous(), mode, uce)
     return _PartialLossFn.apply(logits, target, weights, mode, uce)
 
 
@@ -145,22 +205,62 @@ class _DeepSupFn(torch.autograd.Function):
         return (None, None, None, *[d.permute(0, 4, 1, 2, 3) for d in dls])
 
 
-def deep_supervision_loss(deep_out, target, mask=None, level_weights=DEEP_WEIGHTS):
+class _DeepSupPsFn(torch.autograd.Function):
+    """_DeepSupFn with one supervision row per sample (weights [S, C], u3d_deepsup_loss_ps_fwd/_bwd)."""
+
+    @staticmethod
+    def forward(ctx, target, weights, level_weights, *deep):
+        lgs = [ndhwc_view(l.float()) for l in deep]
+        tgt = target.float().contiguous()
+        L, (S, C) = len(lgs), (lgs[0].shape[0], lgs[0].shape[-1])
+        D, H, W = tgt.shape[-3:]
+        dev = tgt.device
+        sums_ps = torch.empty((L, S, C, 4), dtype=torch.float64, device=dev)
+        pooled = torch.empty((L, C, 5), dtype=torch.float64, device=dev)
+        level_loss = torch.empty(L, dtype=torch.float32, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        ws = ops.WS.get(_lib_query("u3d_deepsup_loss_ps_workspace_bytes", L, C, S), dev, ops.Slot.DEEPSUP_PS)
+        ptrs, dims, lw = _deepsup_host_args(lgs, level_weights)
+        ops.call("u3d_deepsup_loss_ps_fwd", L, ptrs, dims, lw, tgt.data_ptr(), S, D, H, W, C, weights.data_ptr(),
+                 sums_ps.data_ptr(), pooled.data_ptr(), level_loss.data_ptr(), loss.data_ptr(), ws.data_ptr(),
+                 ops._stream())
+        ctx.save_for_backward(tgt, weights, pooled, *lgs)
+        ctx.level_weights = tuple(level_weights)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        tgt, weights, pooled, *lgs = ctx.saved_tensors
+        L, (S, C) = len(lgs), (lgs[0].shape[0], lgs[0].shape[-1])
+        D, H, W = tgt.shape[-3:]
+        go = g.reshape(1).float().contiguous()
+        dls = [torch.empty_like(t) for t in lgs]
+        ptrs, dims, lw = _deepsup_host_args(lgs, ctx.level_weights)
+        dptrs = (ctypes.c_void_p * L)(*[t.data_ptr() for t in dls])
+        ops.call("u3d_deepsup_loss_ps_bwd", L, ptrs, dims, lw, tgt.data_ptr(), S, D, H, W, C, weights.data_ptr(),
+                 pooled.data_ptr(), go.data_ptr(), dptrs, ops._stream())
+        return (None, None, None, *[d.permute(0, 4, 1, 2, 3) for d in dls])
+
+
+def deep_supervision_loss(deep_out, target, mask=None, level_weights=DEEP_WEIGHTS, per_sample=False):
     """get_loss's deep-supervision term (losses.py:119-129): sum over the levels of level_weights[idx] *
     EDiceLoss_partial(C)(l, F.interpolate(target, l.shape[2:], mode='nearest').squeeze(1), soft_max=True, mask=mask,
     uce=False), as one fused multi-level pass each way (u3d_deepsup_loss_fwd/_bwd; the resized targets are never
     built). deep_out: [S, C, d, h, w] logits per level (NCDHW views of NDHWC storage, as the native heads return, are
     read in place; plain NCDHW costs one copy); target [S, 1, D, H, W] (or [S, D, H, W]). More levels than weights
-    raise IndexError (weights[idx]), a level with another C or batch AssertionError, as the reference."""
+    raise IndexError (weights[idx]), a level with another C or batch AssertionError, as the reference.
+    per_sample: ``mask`` holds one row per sample (sample_weights) and every level pools its sums over the samples
+    that supervise the class; the default weights the whole batch with mask[0], as the reference."""
     deep_out = list(deep_out)
     if len(deep_out) == 0:
         raise ValueError("deep_supervision_loss: no levels")
     C = deep_out[0].shape[1]
     check_deep_levels(deep_out, target, C, len(level_weights))
     ops.require_device(target, *deep_out)
-    w = class_weights(mask, C, target.device)
-    return _DeepSupFn.apply(target[:, 0] if target.dim() == 5 else target, w,
-                            tuple(float(x) for x in level_weights[:len(deep_out)]), *deep_out)
+    fn = _DeepSupPsFn if per_sample else _DeepSupFn
+    w = sample_weights(mask, target.shape[0], C, target.device) if per_sample else class_weights(mask, C, target.device)
+    return fn.apply(target[:, 0] if target.dim() == 5 else target, w,
+                    tuple(float(x) for x in level_weights[:len(deep_out)]), *deep_out)
 
 
 def check_deep_levels(deep_out, target, C, n_weights=len(DEEP_WEIGHTS)):

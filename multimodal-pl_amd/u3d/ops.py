@@ -119,6 +119,8 @@ class Slot(enum.Enum):
     S2_CNT = 22          # ZERO
     RING_GB_CNT = 23     # ZERO
     HEAD_CNT = 24        # ZERO: the GN head backward's arrival counter
+    LOSS_PS = 25         # loss, per-sample supervision
+    DEEPSUP_PS = 26      # loss, per-sample supervision
     QUEUE = 40           # ZERO: claim words of the work-stealing ring
     DISC = "disc"        # the discriminator kernels' scratch
 
@@ -1222,6 +1224,29 @@ def partial_loss_bwd(logits, labels, weights, sums, grad_out, softmax=True, uce=
     dl = torch.empty(logits.shape, dtype=out_dtype, device=logits.device)
     call("u3d_partial_loss_bwd", dt_code(out_dtype), logits.data_ptr(), labels.data_ptr(), S, V, C, int(softmax),
          weights.data_ptr(), int(uce), sums.data_ptr(), grad_out.data_ptr(), dl.data_ptr(), _stream())
+    return dl
+
+
+def partial_loss_ps_fwd(logits, labels, weights, softmax=True, uce=True):
+    """partial_loss_fwd with one supervision row per sample: weights fp32 [S, C] -> (loss fp32[1], sums_ps fp64
+    [S, C, 4], pooled fp64 [C, 5] = (I, Z, Y, B, n_c) over the supervising samples)."""
+    S, C = logits.shape[0], logits.shape[-1]
+    V = logits.numel() // (S * C)
+    sums_ps = torch.empty((S, C, 4), dtype=torch.float64, device=logits.device)
+    pooled = torch.empty((C, 5), dtype=torch.float64, device=logits.device)
+    loss = torch.empty((1,), dtype=torch.float32, device=logits.device)
+    ws = WS.get(query("u3d_loss_ps_workspace_bytes", S, V, C), logits.device, Slot.LOSS_PS)
+    call("u3d_partial_loss_ps_fwd", logits.data_ptr(), labels.data_ptr(), S, V, C, int(softmax), weights.data_ptr(),
+         int(uce), sums_ps.data_ptr(), pooled.data_ptr(), loss.data_ptr(), ws.data_ptr(), _stream())
+    return loss, sums_ps, pooled
+
+
+def partial_loss_ps_bwd(logits, labels, weights, pooled, grad_out, softmax=True, uce=True, out_dtype=torch.float32):
+    S, C = logits.shape[0], logits.shape[-1]
+    V = logits.numel() // (S * C)
+    dl = torch.empty(logits.shape, dtype=out_dtype, device=logits.device)
+    call("u3d_partial_loss_ps_bwd", dt_code(out_dtype), logits.data_ptr(), labels.data_ptr(), S, V, C, int(softmax),
+         weights.data_ptr(), int(uce), pooled.data_ptr(), grad_out.data_ptr(), dl.data_ptr(), _stream())
     return dl
 
 

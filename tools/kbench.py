@@ -378,6 +378,18 @@ def _loss(n, s, C, bwd):
     return t_(lambda: ops.partial_loss_bwd(lg, lab, wt, sums, go)), 0.0
 
 
+def _loss_ps(n, s, C, bwd):
+    """_loss with one supervision row per sample (csrc/loss_ps.hip): the same bytes, every sample supervising"""
+    lg = torch.randn((n, s, s, s, C), device=dev)
+    lab = torch.randint(0, C, (n, s, s, s), device=dev).float()
+    wt = torch.ones((n, C), device=dev)
+    if not bwd:
+        return t_(lambda: ops.partial_loss_ps_fwd(lg, lab, wt)), 0.0
+    _, _, pooled = ops.partial_loss_ps_fwd(lg, lab, wt)
+    go = torch.ones(1, device=dev)
+    return t_(lambda: ops.partial_loss_ps_bwd(lg, lab, wt, pooled, go)), 0.0
+
+
 def _stemw(n=2, s=96):
     x = torch.randn((n, 1, s, s, s), device=dev)
     dy = torch.randn((n, s, s, s, 32), device=dev).to(bf)
@@ -453,6 +465,8 @@ CASES["headb96"] = lambda: _head(True)
 CASES["stemw96"] = lambda: _stemw()
 CASES["loss96"] = lambda: _loss(2, 96, 16, False)
 CASES["lossb96"] = lambda: _loss(2, 96, 16, True)
+CASES["loss96_ps"] = lambda: _loss_ps(2, 96, 16, False)
+CASES["lossbwd96_ps"] = lambda: _loss_ps(2, 96, 16, True)
 
 
 if __name__ == "__main__":
