@@ -719,6 +719,29 @@ int u3d_dice_metric_atlas(const float* logits, const float* labels, const float*
                           int C, int num_class, long long* counts, float* metrics, long long* argmax,
                           u3d_stream_t stream);
 
+/* ---------------------------------------------------------------- atlas construction (csrc/atlas_build.hip)
+ * preprocess/atlas_gen_mm.py:114-145: per training case and label l in 1..L, ndimage.zoom(label == l, order=0) to the
+ * atlas shape summed into plane l - 1, a case count per label, then plane / count and gaussian_filter(sigma=3).
+ * u3d_atlas_build_add, one case: label_u8 [h][w][d] label codes (uint8), idx0 [s0], idx1 [s1], idx2 [s2] device int32
+ * source-index tables of the three axes (u3d.data.zoom_index: scipy's zoom(order=0) rule, for output index k of an axis
+ * in -> out: z = (in - 1) / (out - 1) (1 when out == 1), cc = k z in float64, src = floor(cc + 0.5) if cc <= in - 1,
+ * else -1 = "outside": the voxel receives nothing; the table is formed on the host so the index is scipy's bit for
+ * bit). acc fp32 [L][s0][s1][s2], counts int32 [L], 1 <= L <= 31:
+ *   for every (a, b, c) with idx0[a], idx1[b], idx2[c] all >= 0:  l = label[idx0[a]][idx1[b]][idx2[c]];
+ *                                                                 if 1 <= l <= L: acc[l - 1][a][b][c] += 1
+ *   for every l in 1..L that occurs anywhere in label (before the zoom: label_mask.sum() > 0): counts[l - 1] += 1
+ * One pass over the atlas voxels for all labels (one thread owns a voxel: no atomics on acc), one pass over the source
+ * for the presence bits (ws: u3d_atlas_build_ws_bytes, cleared and consumed inside the call). No host read. The sums
+ * are small integers: exact in fp32 up to 2^24 cases, whatever the launch geometry or the order of the calls.
+ * u3d_atlas_build_normalize: out[l][v] = counts[l] > 0 ? (float)((double)acc[l][v] / counts[l]) : 0 for v < V
+ * (the reference skips a label no case has; its plane is all zero). out may be acc. The blur is three
+ * u3d_aug_blur_axis passes with L folded into outer. */
+long long u3d_atlas_build_ws_bytes(void);
+int u3d_atlas_build_add(const unsigned char* label_u8, int h, int w, int d, const int* idx0, const int* idx1,
+                        const int* idx2, int L, int s0, int s1, int s2, float* acc, int* counts, void* ws,
+                        u3d_stream_t stream);
+int u3d_atlas_build_normalize(const float* acc, const int* counts, int L, long long V, float* out, u3d_stream_t stream);
+
 /* ---------------------------------------------------------------- style discriminators (csrc/disc.hip)
  * get_style_discriminator_output (unet3D.py:1832-1849), deep_style_discriminator_output (:1852-1905),
  * norm_style_discriminator_output (:1907-1947), as train_amos_atlas_final.py:320-379 drives them.

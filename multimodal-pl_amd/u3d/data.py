@@ -13,6 +13,10 @@
   (0.75, 1.25), preserve range (p 0.15). Decisions and parameters are drawn on the host with numpy; the kernels apply
   them. batchgenerators is not installed here, so the exact draw sequence is unpinned (each applied operation is
   pinned against numpy / scipy restatements in tests/test_gpu_data.py); the noise uses a counter-based device RNG.
+* ``AtlasBuilder`` / ``build_atlas``: the atlas itself (preprocess/atlas_gen_mm.py:100-145): per case one gather of the
+  label codes through scipy's zoom(order=0) index tables (``zoom_index``, float64 on the host) into per-label sums
+  (u3d_atlas_build_add), then sums / case counts (u3d_atlas_build_normalize) and gaussian_filter(sigma=3) as three
+  u3d_aug_blur_axis passes over all planes. ``average_shape``: the atlas shape of :100-111.
 """
 import math
 
@@ -20,7 +24,7 @@ import numpy as np
 import torch
 
 from . import ops
-from ._lib import call, query
+from ._lib import U3DError, call, query
 
 MODE_COPY, MODE_CT, MODE_MRI = 0, 1, 2
 
@@ -166,3 +170,126 @@ def train_transform(image, rng=np.random, seed=None):
                      ops._stream())
                 log.append(("contrast", b, c, f))
     return x, log
+
+
+def zoom_index(n_in, n_out):
+    """Source index of every output index of scipy.ndimage.zoom(order=0) (mode 'constant', grid_mode False) along an
+    axis resized n_in -> n_out, int32 [n_out]; -1 where scipy takes the coordinate as outside the volume and leaves the
+    voxel 0. scipy's float64 arithmetic: z = (n_in - 1) / (n_out - 1) (1 when n_out == 1), cc = k * z rounded once,
+    floor(cc + 0.5) if cc <= n_in - 1. The "outside" case is real: (n_out - 1) * z rounds to just above n_in - 1 at
+    e.g. 8 -> 26, 22 -> 20, 30 -> 8, 26 -> 12, and the whole last plane of that axis receives nothing."""
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in < 1 or n_out < 1:
+        raise ValueError(f"zoom_index: sizes {n_in} -> {n_out} must be positive")
+    z = np.float64(n_in - 1) / np.float64(n_out - 1) if n_out > 1 else np.float64(1.0)
+    cc = np.arange(n_out, dtype=np.float64) * z
+    src = np.floor(cc + 0.5).astype(np.int64)
+    return np.where(cc <= np.float64(n_in - 1), src, -1).astype(np.int32)
+
+
+def average_shape(shapes):
+    """atlas_gen_mm.py:100-111: per axis the integer sum over the cases, divided by their number, np.round (half to
+    even), int."""
+    shapes = [tuple(int(v) for v in s) for s in shapes]
+    if not shapes or any(len(s) != 3 for s in shapes):
+        raise ValueError("average_shape: needs at least one (H, W, D) shape")
+    total = [sum(s[i] for s in shapes) for i in range(3)]
+    return tuple(int(np.round(t / len(shapes))) for t in total)
+
+
+class AtlasBuilder:
+    """The sums of atlas_gen_mm.py:114-136 on the device. ``acc`` fp32 [L, s0, s1, s2] (voxels of label l + 1 after the
+    zoom, summed over the cases) and ``counts`` int32 [L] (cases that hold label l + 1 before the zoom) are plain
+    sums: partial builders merge by adding them. ``add`` one case at a time, ``finish`` for the atlas."""
+
+    def __init__(self, shape, num_labels=15, device=None):
+        shape = tuple(int(v) for v in shape)
+        if len(shape) != 3 or min(shape) < 1:
+            raise ValueError(f"AtlasBuilder: shape {shape} must be three positive sizes")
+        if not 1 <= int(num_labels) <= 31:
+            raise ValueError(f"AtlasBuilder: num_labels={num_labels} must be in 1..31 (one presence bit per label)")
+        self.shape, self.num_labels = shape, int(num_labels)
+        if device is None and torch.cuda.is_available():
+            device = torch.device("cuda", torch.cuda.current_device())
+        self.device = torch.device(device) if device is not None else None
+        self.acc = self.counts = None
+        self._idx = {}
+        if self.device is not None:
+            if self.device.type != "cuda":
+                raise U3DError(f"AtlasBuilder: device {self.device}: the HIP path needs a ROCm device (no CPU fallback)")
+            self.acc = torch.zeros((self.num_labels,) + shape, dtype=torch.float32, device=self.device)
+            self.counts = torch.zeros(self.num_labels, dtype=torch.int32, device=self.device)
+            self._ws = torch.zeros(query("u3d_atlas_build_ws_bytes"), dtype=torch.uint8, device=self.device)
+
+    def _table(self, n_in, n_out):
+        key = (int(n_in), int(n_out))
+        if key not in self._idx:
+            self._idx[key] = torch.from_numpy(zoom_index(*key)).to(self.device)
+        return self._idx[key]
+
+    def add(self, label):
+        """One case [H, W, D] of label codes (uint8, int16, int32, int64, float32 or float64, on the device). A voxel
+        belongs to label l only if its value equals l exactly: anything that is no integer in 0..255 (257, -255, 1.5,
+        NaN) counts as background and does not wrap onto a label."""
+        if label.dim() != 3 or label.numel() == 0:
+            raise ValueError(f"AtlasBuilder.add: label {tuple(label.shape)} must be a non-empty [H, W, D] volume")
+        ops.require_device(label)
+        if self.acc is None or label.device != self.device:
+            raise ValueError(f"AtlasBuilder.add: label on {label.device}, builder on {self.device}")
+        if label.dtype == torch.uint8:
+            u8 = label.contiguous()
+        elif label.dtype in (torch.int16, torch.int32, torch.int64, torch.float32, torch.float64):
+            ok = (label >= 0) & (label <= 255)
+            if label.is_floating_point():
+                ok &= label == label.floor()
+            u8 = torch.where(ok, label, torch.zeros((), dtype=label.dtype, device=label.device)).to(torch.uint8)
+            u8 = u8.contiguous()
+        else:
+            raise ValueError(f"AtlasBuilder.add: label dtype {label.dtype} not supported")
+        h, w, d = u8.shape
+        s0, s1, s2 = self.shape
+        i0, i1, i2 = self._table(h, s0), self._table(w, s1), self._table(d, s2)
+        with torch.cuda.device(self.device):
+            call("u3d_atlas_build_add", u8.data_ptr(), h, w, d, i0.data_ptr(), i1.data_ptr(), i2.data_ptr(),
+                 self.num_labels, s0, s1, s2, self.acc.data_ptr(), self.counts.data_ptr(), self._ws.data_ptr(),
+                 ops._stream())
+        return self
+
+    def finish(self, sigma=3.0):
+        """acc / counts per label (a label no case holds: zeros, as the reference leaves it), then
+        scipy.ndimage.gaussian_filter(sigma) per label ('reflect', truncate 4; fp32 weights, fp64 accumulation);
+        sigma None or 0: no filter. fp32 [L, s0, s1, s2]; the builder stays usable for more add calls."""
+        if self.acc is None:
+            raise U3DError("AtlasBuilder.finish: no ROCm device (no CPU fallback)")
+        L, (s0, s1, s2) = self.num_labels, self.shape
+        cur = torch.empty_like(self.acc)
+        with torch.cuda.device(self.device):
+            call("u3d_atlas_build_normalize", self.acc.data_ptr(), self.counts.data_ptr(), L, s0 * s1 * s2,
+                 cur.data_ptr(), ops._stream())
+            if sigma:
+                w, r = gaussian_kernel1d(sigma)
+                wt = torch.from_numpy(w).to(self.device)
+                nxt = torch.empty_like(cur)
+                for outer, n, inner in ((L, s0, s1 * s2), (L * s0, s1, s2), (L * s0 * s1, s2, 1)):
+                    call("u3d_aug_blur_axis", cur.data_ptr(), nxt.data_ptr(), outer, n, inner, wt.data_ptr(), r,
+                         ops._stream())
+                    cur, nxt = nxt, cur
+        return cur
+
+
+def build_atlas(labels, shape=None, num_labels=15, sigma=3.0):
+    """atlas_gen_mm.py:100-145 on an iterable of device label volumes [H, W, D]: shape None takes their
+    average_shape (the iterable is then held as a list). Returns the fp32 atlas [num_labels, s0, s1, s2], ready for
+    crop_patch(..., atlas=atlas[:13]). Reading the files and choosing the training cases stay with the caller."""
+    if shape is None:
+        labels = list(labels)
+        shape = average_shape([lab.shape for lab in labels])
+    builder = None
+    for lab in labels:
+        ops.require_device(lab)
+        if builder is None:
+            builder = AtlasBuilder(shape, num_labels, lab.device)
+        builder.add(lab)
+    if builder is None:
+        raise ValueError("build_atlas: no label volumes")
+    return builder.finish(sigma)
