@@ -742,6 +742,44 @@ int u3d_atlas_build_add(const unsigned char* label_u8, int h, int w, int d, cons
                         u3d_stream_t stream);
 int u3d_atlas_build_normalize(const float* acc, const int* counts, int L, long long V, float* out, u3d_stream_t stream);
 
+/* ---------------------------------------------------------------- connected components, body mask (csrc/ccl.hip)
+ * preprocess/forward_crop.py:37-82 (getmaxcomponent, get_body) and the bounding boxes of :157-193.
+ * u3d_ccl_label: mask uint8 [Z][Y][X] (nonzero = foreground) -> labels int32 [Z][Y][X]: face connectivity (6
+ * neighbours), components numbered 1..n in the C order of their first voxel, background 0, i.e.
+ * scipy.ndimage.label(mask) with its default structure; *n (device int) = the number of components. A single-pass
+ * union-find whose roots are the smallest linear index of their component (csrc/ccl_core.h), so the result does not
+ * depend on the launch geometry; no host read, no pass repeated until convergence. Z * Y * X < 2^31 (U3D_EINVAL
+ * otherwise, checked before any pointer is used). ws: u3d_ccl_ws_bytes(V) bytes (-1 for V < 1 or V >= 2^31), contents
+ * undefined on entry and exit. u3d_ccl_tile: the extents of the tile one workgroup labels in LDS (for tests that
+ * straddle the seams).
+ * u3d_ccl_select, getmaxcomponent(mask, num_limit, min_filter) on labels / n of u3d_ccl_label: among the labels
+ * 1..min(num_limit - 1, n) with size >= min_filter (compared in double) the largest, the earliest on a tie;
+ * mask_out uint8 [Z][Y][X] = (labels == chosen), all zero when none qualifies. 1 <= num_limit <= 1024.
+ * ws: u3d_ccl_select_ws_bytes(). record, device int32[U3D_CCL_RECORD]:
+ *   {found, label, size, lo z, lo y, lo x, hi z, hi y, hi x (inclusive; lo = INT_MAX, hi = -1 when empty), n, 0, 0}
+ * u3d_body_threshold: out uint8 = vol > t in fp32 (NaN: 0); erode != 0: AND over [z-1..z][y-1..y][x-1..x] with outside
+ * false (binary_erosion with a 2 x 2 x 2 structure) in the same pass.
+ * u3d_mask_window_axis: in / out uint8 [outer][n][inner], out[o][i][k] = AND (op 0) or OR (op 1) of in[o][j][k] != 0
+ * over j in [i + lo, i + hi], a j outside [0, n) counting as false: scipy's binary_erosion / binary_dilation with a
+ * box of size m per axis is op 0 with (lo, hi) = (-(m / 2), m - 1 - m / 2), op 1 with (-(m - 1 - m / 2), m / 2).
+ * u3d_nonzero_bbox: bounding box and count of x != 0 (dtype 0 uint8, 1 float32, 2 int32; NaN counts) into record
+ * (found stays as it is, size += count, lo / hi min / max); accumulate == 0 resets the record first.
+ * gate (nullable device int): when *gate != 0 the call does nothing. With gate = &record[0] of a u3d_ccl_select the
+ * fallback route of get_body queues behind the component search without a host read. */
+#define U3D_CCL_RECORD 12
+void u3d_ccl_tile(int* tz, int* ty, int* tx);
+long long u3d_ccl_ws_bytes(long long V);
+long long u3d_ccl_select_ws_bytes(void);
+int u3d_ccl_label(const unsigned char* mask, int Z, int Y, int X, int* labels, int* n, void* ws, u3d_stream_t stream);
+int u3d_ccl_select(const int* labels, int Z, int Y, int X, const int* n, int num_limit, double min_filter,
+                   unsigned char* mask_out, int* record, void* ws, u3d_stream_t stream);
+int u3d_body_threshold(const float* vol, int Z, int Y, int X, float t, int erode, unsigned char* out, const int* gate,
+                       u3d_stream_t stream);
+int u3d_mask_window_axis(const unsigned char* in, unsigned char* out, long long outer, int n, long long inner, int lo,
+                         int hi, int op, const int* gate, u3d_stream_t stream);
+int u3d_nonzero_bbox(const void* x, int dtype, int Z, int Y, int X, int* record, int accumulate, const int* gate,
+                     u3d_stream_t stream);
+
 /* ---------------------------------------------------------------- style discriminators (csrc/disc.hip)
  * get_style_discriminator_output (unet3D.py:1832-1849), deep_style_discriminator_output (:1852-1905),
  * norm_style_discriminator_output (:1907-1947), as train_amos_atlas_final.py:320-379 drives them.

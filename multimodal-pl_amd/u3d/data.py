@@ -17,6 +17,11 @@
   label codes through scipy's zoom(order=0) index tables (``zoom_index``, float64 on the host) into per-label sums
   (u3d_atlas_build_add), then sums / case counts (u3d_atlas_build_normalize) and gaussian_filter(sigma=3) as three
   u3d_aug_blur_axis passes over all planes. ``average_shape``: the atlas shape of :100-111.
+* ``label_components`` / ``largest_component`` / ``get_body`` / ``bounding_box`` / ``body_crop``: the body mask and the
+  three crops of preprocess/forward_crop.py (:37-82 getmaxcomponent / get_body, :148-207) on 3-D connected components
+  labelled on the device (csrc/ccl.hip: a single-pass union-find, scipy.ndimage.label's numbering). get_body queues
+  its box-opening fallback behind the component search, gated on the device by the search's record, so a case costs
+  three small host reads: the label range and the two body records.
 """
 import math
 
@@ -293,3 +298,204 @@ def build_atlas(labels, shape=None, num_labels=15, sigma=3.0):
     if builder is None:
         raise ValueError("build_atlas: no label volumes")
     return builder.finish(sigma)
+
+
+# ------------------------------------------------------------------------------------------------ body mask and crop
+REC_LEN = 12                     # U3D_CCL_RECORD: {found, label, size, lo z y x, hi z y x, n, 0, 0}
+ROUTE_COMPONENT, ROUTE_FALLBACK = 0, 1
+_BBOX_DTYPES = {torch.uint8: 0, torch.float32: 1, torch.int32: 2}
+
+
+def ccl_tile():
+    """(tz, ty, tx): the tile one workgroup labels in LDS before the seams are joined."""
+    import ctypes
+    t = [ctypes.c_int(0) for _ in range(3)]
+    query("u3d_ccl_tile", *(ctypes.byref(v) for v in t))
+    return tuple(v.value for v in t)
+
+
+def _volume3(x, what):
+    if x.dim() != 3 or x.numel() == 0:
+        raise ValueError(f"{what}: {tuple(x.shape)} must be a non-empty [Z, Y, X] volume")
+    ops.require_device(x)
+    if x.numel() >= 2 ** 31:
+        raise ValueError(f"{what}: {x.numel()} voxels (the labelling indexes voxels with int32: fewer than 2^31)")
+
+
+def _mask_u8(mask):
+    if mask.dtype == torch.bool:
+        return mask.contiguous().view(torch.uint8)
+    if mask.dtype == torch.uint8:
+        return mask.contiguous()
+    return (mask != 0).view(torch.uint8).contiguous()
+
+
+def _label(m8):
+    """labels int32 [Z, Y, X] and the device int n of a uint8 mask; no host read."""
+    Z, Y, X = m8.shape
+    labels = torch.empty((Z, Y, X), dtype=torch.int32, device=m8.device)
+    n = torch.empty(1, dtype=torch.int32, device=m8.device)
+    ws = torch.empty(query("u3d_ccl_ws_bytes", m8.numel()), dtype=torch.uint8, device=m8.device)
+    call("u3d_ccl_label", m8.data_ptr(), Z, Y, X, labels.data_ptr(), n.data_ptr(), ws.data_ptr(), ops._stream())
+    return labels, n
+
+
+def _select(labels, n, num_limit, min_filter):
+    """(mask uint8, record int32[REC_LEN]) of getmaxcomponent on device labels; no host read."""
+    if not 1 <= int(num_limit) <= 1024:
+        raise ValueError(f"largest_component: num_limit={num_limit} must be in 1..1024")
+    Z, Y, X = labels.shape
+    out = torch.empty((Z, Y, X), dtype=torch.uint8, device=labels.device)
+    rec = torch.empty(REC_LEN, dtype=torch.int32, device=labels.device)
+    ws = torch.empty(query("u3d_ccl_select_ws_bytes"), dtype=torch.uint8, device=labels.device)
+    call("u3d_ccl_select", labels.data_ptr(), Z, Y, X, n.data_ptr(), int(num_limit), float(min_filter), out.data_ptr(),
+         rec.data_ptr(), ws.data_ptr(), ops._stream())
+    return out, rec
+
+
+def label_components(mask):
+    """scipy.ndimage.label(mask) on the device: mask [Z, Y, X] of any dtype (nonzero = foreground) -> (labels int32
+    [Z, Y, X], n). Face connectivity; components numbered 1..n in the C order of their first voxel. The int n is the
+    one host read."""
+    _volume3(mask, "label_components")
+    with torch.cuda.device(mask.device):
+        labels, n = _label(_mask_u8(mask))
+        return labels, int(n.item())
+
+
+def largest_component(mask, num_limit=10, min_filter=1e6):
+    """forward_crop.py:37-59 (getmaxcomponent): among the components 1..num_limit-1 with at least min_filter voxels
+    the largest, the earliest on a tie, as a uint8 mask; None when none qualifies (one host read of the record)."""
+    _volume3(mask, "largest_component")
+    with torch.cuda.device(mask.device):
+        labels, n = _label(_mask_u8(mask))
+        out, rec = _select(labels, n, num_limit, min_filter)
+        return out if int(rec[0].item()) else None
+
+
+def _window3(cur, size, dilate, gate):
+    """Box erosion (AND) / dilation (OR) of a uint8 volume, one u3d_mask_window_axis pass per axis."""
+    Z, Y, X = cur.shape
+    lo, hi = -(size // 2), size - 1 - size // 2
+    if dilate:
+        lo, hi = -hi, -lo
+    for outer, n, inner in ((1, Z, Y * X), (Z, Y, X), (Z * Y, X, 1)):
+        nxt = torch.empty_like(cur)
+        call("u3d_mask_window_axis", cur.data_ptr(), nxt.data_ptr(), outer, n, inner, lo, hi, 1 if dilate else 0, gate,
+             ops._stream())
+        cur = nxt
+    return cur
+
+
+def _get_body(volume, threshold_all, min_filter, fallback_threshold):
+    """(mask uint8, record): the record's found says which route produced the mask; size, lo, hi describe the mask of
+    either route. Everything is queued on the stream; nothing is read."""
+    vol = volume.float().contiguous()
+    Z, Y, X = vol.shape
+    s = ops._stream()
+    m = torch.empty((Z, Y, X), dtype=torch.uint8, device=vol.device)
+    call("u3d_body_threshold", vol.data_ptr(), Z, Y, X, float(threshold_all), 1, m.data_ptr(), None, s)
+    labels, n = _label(m)
+    out, rec = _select(labels, n, 100, min_filter)
+    # the fallback (:76-80), gated on the device by rec[0] = found: no-ops when a component was chosen
+    gate = rec.data_ptr()
+    fb = float(threshold_all if fallback_threshold is None else fallback_threshold)
+    call("u3d_body_threshold", vol.data_ptr(), Z, Y, X, fb, 0, m.data_ptr(), gate, s)
+    opened = _window3(_window3(m, 10, False, gate), 10, True, gate)
+    call("u3d_nonzero_bbox", opened.data_ptr(), 0, Z, Y, X, rec.data_ptr(), 1, gate, s)
+    return out, opened, rec
+
+
+def get_body(volume, threshold_all=-200, min_filter=1e6, fallback_threshold=None):
+    """forward_crop.py:62-82: volume > threshold_all (strict, fp32, NaN false), eroded by a 2 x 2 x 2 box, then the
+    largest of its first 99 components with at least min_filter voxels; when there is none, volume >
+    fallback_threshold (default threshold_all; the reference reads its global there, equal in every call it makes)
+    opened by a 10^3 box. uint8 [Z, Y, X]."""
+    _volume3(volume, "get_body")
+    with torch.cuda.device(volume.device):
+        out, opened, rec = _get_body(volume, threshold_all, min_filter, fallback_threshold)
+        return out if int(rec[0].item()) else opened
+
+
+def _record(rec):
+    r = rec.cpu().tolist()
+    return {"found": bool(r[0]), "label": r[1], "size": r[2], "lo": tuple(r[3:6]), "hi": tuple(r[6:9]), "n": r[9]}
+
+
+def _bbox_record(x):
+    _volume3(x, "bounding_box")
+    if x.dtype not in _BBOX_DTYPES:
+        x = _mask_u8(x)
+    x = x.contiguous()
+    rec = torch.empty(REC_LEN, dtype=torch.int32, device=x.device)
+    with torch.cuda.device(x.device):
+        call("u3d_nonzero_bbox", x.data_ptr(), _BBOX_DTYPES[x.dtype], *x.shape, rec.data_ptr(), 0, None, ops._stream())
+    return rec
+
+
+def bounding_box(x):
+    """((z0, y0, x0), (z1, y1, x1)) of the nonzero voxels of a [Z, Y, X] device tensor, max inclusive (one host read);
+    ValueError when there is none, as np.min of an empty index list."""
+    r = _record(_bbox_record(x))
+    if r["size"] == 0:
+        raise ValueError("bounding_box: no nonzero voxel")
+    return r["lo"], r["hi"]
+
+
+def body_threshold(cid):
+    """forward_crop.py:166-172: 30000 for the case ids 540 and 518, 25 for other ids > 410 (MRI), -200 otherwise (CT)."""
+    cid = int(cid)
+    if cid in (540, 518):
+        return 30000
+    return 25 if cid > 410 else -200
+
+
+def body_crop(image, label, cid, min_filter=1e6, min_filter_up=1e5):
+    """forward_crop.py:148-207 on device tensors image / label [Z, Y, X]: label codes >= 14 cleared; image and label
+    cropped along x to the label's range (margin 1); the body of the image (get_body at body_threshold(cid)) and its
+    bounding box with margin 3; the body of the upper half image[:, :, :w // 2 + 10] (min_filter_up) and its z range
+    with margin 5; when the full body is more than 30 planes longer in z than the upper half's and cid > 500 ("find
+    hand"), the z slice [zmin_up:zmax_up] of the already cropped arrays, as the reference applies it.
+    Returns (image_a, label_a, info): slices of image and of the cleared label; info holds label_range, bbox, bbox_up
+    (min, inclusive max), size, size_up, route, route_up (ROUTE_COMPONENT / ROUTE_FALLBACK), inter_all, inter_up,
+    found_hand, mask (the body mask as the reference leaves it), label_sum_before / _after (0-dim device tensors: the
+    reference's consistency print). Three host reads: the label range and the two body records. An empty label or an
+    empty body raises ValueError."""
+    _volume3(image, "body_crop")
+    _volume3(label, "body_crop")
+    if image.shape != label.shape or image.device != label.device:
+        raise ValueError(f"body_crop: image {tuple(image.shape)} on {image.device}, label {tuple(label.shape)} on "
+                         f"{label.device}")
+    with torch.cuda.device(image.device):
+        label = torch.where(label >= 14, torch.zeros((), dtype=label.dtype, device=label.device), label)
+        sum_before = label.double().sum()
+        lr = _record(_bbox_record(label))                                            # host read 1
+        if lr["size"] == 0:
+            raise ValueError("body_crop: the label has no voxel in 1..13")
+        xmin, xmax = max(0, lr["lo"][2] - 1), lr["hi"][2] + 1
+        image, label = image[:, :, xmin:xmax], label[:, :, xmin:xmax]
+        thre = body_threshold(cid)
+        comp, opened, rec = _get_body(image, thre, min_filter, None)
+        r = _record(rec)                                                             # host read 2
+        if r["size"] == 0:
+            raise ValueError("body_crop: the body mask is empty")
+        mask = comp if r["found"] else opened
+        zmin, ymin, x0 = (max(0, v - 3) for v in r["lo"])
+        zmax, ymax, x1 = (v + 3 for v in r["hi"])
+        image_a, label_a = image[zmin:zmax, ymin:ymax, x0:x1], label[zmin:zmax, ymin:ymax, x0:x1]
+        comp_up, opened_up, rec_up = _get_body(image[:, :, :image_a.shape[2] // 2 + 10], thre, min_filter_up, None)
+        u = _record(rec_up)                                                          # host read 3
+        if u["size"] == 0:
+            raise ValueError("body_crop: the body mask of the upper half is empty")
+        zmin_up, zmax_up = max(0, u["lo"][0] - 5), u["hi"][0] + 5
+        inter_all, inter_up = zmax - zmin, zmax_up - zmin_up
+        hand = inter_all - inter_up > 30 and int(cid) > 500
+        if hand:
+            image_a, label_a, mask = image_a[zmin_up:zmax_up], label_a[zmin_up:zmax_up], mask[zmin_up:zmax_up]
+        info = {"label_range": (xmin, xmax), "bbox": (r["lo"], r["hi"]), "bbox_up": (u["lo"], u["hi"]),
+                "size": r["size"], "size_up": u["size"],
+                "route": ROUTE_COMPONENT if r["found"] else ROUTE_FALLBACK,
+                "route_up": ROUTE_COMPONENT if u["found"] else ROUTE_FALLBACK,
+                "inter_all": inter_all, "inter_up": inter_up, "found_hand": bool(hand), "mask": mask,
+                "label_sum_before": sum_before, "label_sum_after": label_a.double().sum()}
+        return image_a, label_a, info
