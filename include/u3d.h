@@ -780,6 +780,45 @@ int u3d_mask_window_axis(const unsigned char* in, unsigned char* out, long long 
 int u3d_nonzero_bbox(const void* x, int dtype, int Z, int Y, int X, int* record, int accumulate, const int* gate,
                      u3d_stream_t stream);
 
+/* ---------------------------------------------------------------- distance transform, surface metrics (csrc/edt.hip)
+ * Volumes are [Z][Y][X]; spacing (sz, sy, sx) in the same order. Additive: no reference line (u3d/surface.py).
+ * u3d_edt: mask uint8 -> out fp32, for every voxel the Euclidean distance (squared != 0: its square) to the nearest
+ * feature voxel; a feature is a nonzero voxel, or a zero voxel when invert != 0. Exact: separable, squared distances in
+ * fp64 with w = spacing^2 (csrc/edt_core.h); with integer spacings every product and sum is exact, the root is the
+ * correctly rounded fp64 root rounded once to fp32. A mask without a feature gives +inf everywhere. No atomics: a pure
+ * function of the mask. Extents at most u3d_edt_max_extent() per axis and Z * Y * X < 2^31, spacings positive
+ * (U3D_EINVAL otherwise, checked before any pointer is used or anything is launched). ws: u3d_edt_ws_bytes(V) bytes
+ * (-1 for V < 1 or V >= 2^31), contents undefined on entry and exit. u3d_edt_tile: the min-plus passes solve
+ * min(max_cols, largest power of two <= tile_bytes / (8 n)) adjacent lines of length n per workgroup (for tests that
+ * straddle those thresholds).
+ * Source dtypes of the two calls below: 0 uint8, 1 float32, 2 int32, 3 int64.
+ * u3d_mask_surface: out uint8 [bz][by][bx] on the box at (z0, y0, x0) inside the volume: (src == value) and not all six
+ * face neighbours == value, a neighbour outside the volume counting as different: m & ~binary_erosion(m) with scipy's
+ * default structure and border_value 0. nonzero != 0: src != 0 in place of src == value (NaN counts). value is compared
+ * in double. One pass.
+ * u3d_class_boxes: record int32 [num_class][U3D_CLASS_RECORD], for class c = 1..num_class at record[c - 1]:
+ *   {lo z, lo y, lo x, hi z, hi y, hi x (inclusive) of (pred == c) | (gt == c); lo = INT_MAX, hi = -1 when empty,
+ *    voxels of pred == c, voxels of gt == c}
+ * in one launch (block-reduced in LDS, one atomic per block, bound and class). 1 <= num_class <= 64; a voxel whose
+ * value is no integer in 1..num_class belongs to no class.
+ * u3d_surface_dist_reduce: over the voxels with surf_a != 0, record fp64[U3D_SURFACE_RECORD] =
+ *   {count, sum of dist_b (fp64, fixed order), max (-inf when count == 0), count of dist_b <= tol, min (+inf)}.
+ * ws: u3d_surface_reduce_ws_bytes(). */
+#define U3D_CLASS_RECORD 8
+#define U3D_SURFACE_RECORD 5
+int u3d_edt_max_extent(void);
+void u3d_edt_tile(int* max_cols, int* tile_bytes);
+long long u3d_edt_ws_bytes(long long V);
+long long u3d_surface_reduce_ws_bytes(void);
+int u3d_edt(const unsigned char* mask, int Z, int Y, int X, double sz, double sy, double sx, int invert, int squared,
+            float* out, void* ws, u3d_stream_t stream);
+int u3d_mask_surface(const void* src, int dtype, int Z, int Y, int X, double value, int nonzero, int z0, int y0, int x0,
+                     int bz, int by, int bx, unsigned char* out, u3d_stream_t stream);
+int u3d_class_boxes(const void* pred, int pred_dtype, const void* gt, int gt_dtype, int Z, int Y, int X, int num_class,
+                    int* record, u3d_stream_t stream);
+int u3d_surface_dist_reduce(const unsigned char* surf_a, const float* dist_b, long long V, double tol, double* record,
+                            void* ws, u3d_stream_t stream);
+
 /* ---------------------------------------------------------------- style discriminators (csrc/disc.hip)
  * get_style_discriminator_output (unet3D.py:1832-1849), deep_style_discriminator_output (:1852-1905),
  * norm_style_discriminator_output (:1907-1947), as train_amos_atlas_final.py:320-379 drives them.

@@ -125,6 +125,35 @@ def get_dice2(preds, labels, t_id, atlas=None, num_class=13):
     return dices, senc, spec, am
 
 
+def get_surface_scores(preds, labels, t_id, num_class=13, spacing=(1, 1, 1), tolerance=1.0):
+    """Boundary metrics next to get_dice's overlap counts (additive: the reference reports none): returns
+    (nsd, hd95, assd, argmax), three lists of num_class 0-dim device tensors, each the mean over the batch as dice_score
+    takes it (NaN and inf propagate), and the label map. preds: logits [S, C, D, H, W] (the argmax is taken as get_dice
+    takes it) or an integer label map [S, D, H, W]; labels [S, 1, D, H, W] or [S, D, H, W]. spacing (sd, sh, sw) and
+    tolerance (a float or num_class of them, in spacing units) as u3d.surface.surface_metrics, which defines the
+    metrics: the normalised surface Dice at the tolerance, the 95th-percentile Hausdorff distance and the average
+    symmetric surface distance of the voxel surfaces. CPU tensors raise U3DError."""
+    from u3d.surface import surface_metrics_fp64
+    ops.require_device(preds, labels)
+    if preds.dim() == 5:
+        lg = ndhwc_view(preds.float())  # get_dice's fused pass, for its argmax map
+        lab = labels.float().reshape(preds.shape[0], -1).contiguous()
+        _, _, am = ops.dice_metric(lg, lab, num_class, want_argmax=True)
+    elif preds.dim() == 4 and not preds.dtype.is_floating_point:
+        am = preds
+    else:
+        raise ValueError(f"get_surface_scores: preds {tuple(preds.shape)} ({preds.dtype}) must be logits "
+                         "[S, C, D, H, W] or an integer label map [S, D, H, W]")
+    if labels.dim() == 5 and labels.shape[1] == 1:
+        labels = labels[:, 0]
+    if labels.shape != am.shape:
+        raise ValueError(f"get_surface_scores: labels {tuple(labels.shape)} vs label map {tuple(am.shape)}")
+    m = surface_metrics_fp64(am, labels, num_class=num_class, spacing=spacing, tolerance=tolerance)
+    m = m.mean(dim=0).float()  # the batch mean in fp64, one fp32 store
+    return ([m[l, 0] for l in range(num_class)], [m[l, 2] for l in range(num_class)],
+            [m[l, 3] for l in range(num_class)], am)
+
+
 def _gaussian_profiles(patch_size, sigma_scale=1.0 / 8):
     """The 1-D factors of _get_gaussian (evaluate_amos.py:184-197): scipy.ndimage.gaussian_filter (truncate 4.0,
     mode 'constant') of a centred delta is the product of three normalised 1-D kernels; each factor is scaled
