@@ -819,6 +819,32 @@ int u3d_class_boxes(const void* pred, int pred_dtype, const void* gt, int gt_dty
 int u3d_surface_dist_reduce(const unsigned char* surf_a, const float* dist_b, long long V, double tol, double* record,
                             void* ws, u3d_stream_t stream);
 
+/* ---------------------------------------------------------------- grid resampling (csrc/resample.hip)
+ * The sampling of MONAI's Orientationd + Spacingd (preprocess/transforms.py:41-54: trilinear image, nearest label,
+ * padding_mode "border") and its inverse for predictions. The map from an output voxel to the source is separable: per
+ * output axis a = 0, 1, 2 the source axis it reads (src_stride[a] in elements, src_n[a] its length) and a table over
+ * the n_out[a] output indices, formed in float64 on the host (u3d.data.GridPlan) from the axis' source coordinate
+ * c(k) = clip(scale k + offset, 0, n - 1):
+ *   i0[k] = min(floor(c), max(n - 2, 0)), frac[k] = c - i0[k]  (linear);   near[k] = rint(c), half to even  (nearest)
+ * and on a flipped axis the mirror of that: i0 -> n - 1 - min(i0 + 1, n - 1), frac -> 1 - frac, near -> n - 1 - near
+ * (the same two taps with the same weights), so a kernel never sees a permutation or a flip. src has C channels src_chan_stride elements apart; out is
+ * [C][n_out[0]][n_out[1]][n_out[2]] contiguous. Tables are device pointers; src_stride, src_n, n_out host arrays of 3.
+ * u3d_grid_resample_linear: src fp32 or int16 -> out fp32. Eight taps (i0, i1 = min(i0 + 1, n - 1)) per axis pair,
+ *   v = lerp along axis 2, then 1, then 0 in fp64 with lerp(a, b, f) = a + f (b - a), rounded once to fp32.
+ * u3d_grid_resample_nearest: src uint8, int16, int32 or fp32 -> out of the same type, out[k] = src[near0, near1, near2].
+ * Every table entry is clamped to [0, n - 1] before use. n_out[0] * n_out[1] < 2^31 - 256; offsets are 64-bit. */
+#define U3D_RS_U8 0
+#define U3D_RS_I16 1
+#define U3D_RS_I32 2
+#define U3D_RS_F32 3
+int u3d_grid_resample_linear(const void* src, int src_dtype, int C, const long long* src_stride,
+                             long long src_chan_stride, const int* src_n, const int* n_out, const int* i0_0,
+                             const int* i0_1, const int* i0_2, const double* frac_0, const double* frac_1,
+                             const double* frac_2, float* out, u3d_stream_t stream);
+int u3d_grid_resample_nearest(const void* src, int src_dtype, int C, const long long* src_stride,
+                              long long src_chan_stride, const int* src_n, const int* n_out, const int* near_0,
+                              const int* near_1, const int* near_2, void* out, u3d_stream_t stream);
+
 /* ---------------------------------------------------------------- style discriminators (csrc/disc.hip)
  * get_style_discriminator_output (unet3D.py:1832-1849), deep_style_discriminator_output (:1852-1905),
  * norm_style_discriminator_output (:1907-1947), as train_amos_atlas_final.py:320-379 drives them.

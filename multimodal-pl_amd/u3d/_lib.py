@@ -173,6 +173,8 @@ _SIGS = {
     "u3d_mask_surface": [P, I, I, I, I, D, I, I, I, I, I, I, I, P, P],
     "u3d_class_boxes": [P, I, P, I, I, I, I, I, P, P],
     "u3d_surface_dist_reduce": [P, P, L, D, P, P, P],
+    "u3d_grid_resample_linear": [P, I, I, P, L, P, P, P, P, P, P, P, P, P, P],
+    "u3d_grid_resample_nearest": [P, I, I, P, L, P, P, P, P, P, P, P],
     "u3d_disc_conv_fwd_splits": [I, I, I, I, I, I],
     "u3d_disc_conv_fwd_ws_bytes": [I, I, I, I, I, I],
     "u3d_disc_conv_fwd": [I, P, I, I, I, I, I, I, I, P, P, P, I, I, I, I, P, P],

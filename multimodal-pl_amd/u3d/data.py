@@ -22,6 +22,14 @@
   labelled on the device (csrc/ccl.hip: a single-pass union-find, scipy.ndimage.label's numbering). get_body queues
   its box-opening fallback behind the component search, gated on the device by the search's record, so a case costs
   three small host reads: the label range and the two body records.
+* ``spacing_plan`` / ``GridPlan`` / ``resample_spacing`` / ``preprocess_case``: MONAI's Orientationd + Spacingd as
+  preprocess/transforms.py:41-54 applies them (forward_crop.py:121-146), and the way back for predictions
+  (``GridPlan.inverse``). With Spacing's defaults the resampling is a permutation and flip of the axes followed by an
+  independent scale per axis, so the grid is a few float64 operations on the host (``orientation_of``: nibabel's
+  io_orientation) and the sampling a gather through three per-axis tables (csrc/resample.hip: trilinear in fp64 with
+  border clamping, or nearest). monai is not installed here: the sampling is pinned to torch's grid_sample on float64
+  (the engine MONAI calls) and to scipy's map_coordinates, the output grid to its formulas; bit parity with one MONAI
+  release is not pinned, in particular the output size where (n - 1) s / p + 1 is a half-integer (``out_shape=``).
 """
 import math
 
@@ -499,3 +507,250 @@ def body_crop(image, label, cid, min_filter=1e6, min_filter_up=1e5):
                 "inter_all": inter_all, "inter_up": inter_up, "found_hand": bool(hand), "mask": mask,
                 "label_sum_before": sum_before, "label_sum_after": label_a.double().sum()}
         return image_a, label_a, info
+
+
+# ------------------------------------------------------------------------------------- orientation and spacing
+AXIS_CODES = (("L", "R"), ("P", "A"), ("I", "S"))        # world axis -> (code of its negative, of its positive end)
+RS_U8, RS_I16, RS_I32, RS_F32 = 0, 1, 2, 3               # U3D_RS_* (include/u3d.h)
+_RS_DTYPES = {torch.uint8: RS_U8, torch.int16: RS_I16, torch.int32: RS_I32, torch.float32: RS_F32}
+
+
+def _affine44(affine):
+    a = np.array(affine.detach().cpu().numpy() if isinstance(affine, torch.Tensor) else affine, dtype=np.float64)
+    if a.shape != (4, 4) or not np.isfinite(a).all():
+        raise ValueError(f"affine: a finite 4 x 4 matrix is needed, got shape {a.shape}")
+    if np.linalg.matrix_rank(a[:3, :3]) < 3:
+        raise ValueError("affine: the 3 x 3 block is singular")
+    return a
+
+
+def orientation_of(affine):
+    """nibabel's io_orientation: ((out_axis, sign), ...) per index axis of a 4 x 4 index-to-world affine (RAS+): the
+    world axis each index axis runs closest to, and in which direction. Columns divided by their norms (a zero norm
+    counts as 1), R = P[:, keep] @ Qs[keep] of their SVD with keep = S > S.max() * 3 * eps, then greedily for the axes
+    0, 1, 2: out_axis = argmax |R[:, ax]|, its sign, and row out_axis of R zeroed."""
+    a = _affine44(affine)
+    rzs = a[:3, :3]
+    zooms = np.sqrt(np.sum(rzs * rzs, axis=0))
+    zooms[zooms == 0] = 1
+    rs = rzs / zooms
+    P, S, Qs = np.linalg.svd(rs, full_matrices=False)
+    keep = S > S.max() * 3 * np.finfo(S.dtype).eps
+    R = np.dot(P[:, keep], Qs[keep])
+    out = []
+    for ax in range(3):
+        col = R[:, ax]
+        o = int(np.argmax(np.abs(col)))
+        out.append((o, -1 if col[o] < 0 else 1))
+        R[o, :] = 0
+    if sorted(o for o, _ in out) != [0, 1, 2]:
+        raise ValueError("affine: the index axes do not map onto three different world axes")
+    return tuple(out)
+
+
+def axcodes_of(affine):
+    """The orientation as axis codes, e.g. "LPS": per index axis the end of the world axis it runs towards."""
+    return "".join(AXIS_CODES[o][(s + 1) // 2] for o, s in orientation_of(affine))
+
+
+def _target_orientation(axcodes):
+    codes = tuple(str(axcodes).upper()) if isinstance(axcodes, str) else tuple(str(c).upper() for c in axcodes)
+    out = []
+    for c in codes:
+        hit = [(w, 2 * e - 1) for w, pair in enumerate(AXIS_CODES) for e in (0, 1) if pair[e] == c]
+        if not hit:
+            raise ValueError(f"axcodes {axcodes!r}: unknown code {c!r} (L R P A I S)")
+        out.append(hit[0])
+    if len(out) != 3 or sorted(w for w, _ in out) != [0, 1, 2]:
+        raise ValueError(f"axcodes {axcodes!r}: three codes, one per world axis, are needed")
+    return out
+
+
+class GridPlan:
+    """A separable resampling between two voxel grids: output axis i reads source axis perm[i] at the coordinate
+    c(k) = clip(scale[i] * k + offset[i], 0, n - 1) (n = src_shape[perm[i]]), mirrored to n - 1 - c when flip[i].
+    ``tables[i]`` = (i0 int32, frac float64, near int32) over the out_shape[i] output indices, in indices of the source
+    axis as stored (the flip is inside them). On the reoriented axis the taps are (j0, j1 = min(j0 + 1, n - 1)) with
+    j0 = min(floor(c), max(n - 2, 0)) and the weight f = c - j0 on j1, the nearest index rint(c), half to even
+    (grid_sample's rule). Stored:
+        not flipped   i0 = j0,          frac = f,      near = rint(c)
+        flipped       i0 = n - 1 - j1,  frac = 1 - f,  near = n - 1 - rint(c)
+    so the kernel's pair (i0, min(i0 + 1, n - 1)) is the same two voxels with the same weights either way
+    (the nearest index is rounded before the mirror, as a flip followed by grid_sample rounds it). src_affine /
+    out_affine: the index-to-world affines of the two grids. ``apply`` runs the kernels, ``inverse`` gives the way
+    back."""
+
+    def __init__(self, src_shape, out_shape, perm, flip, scale, offset, src_affine, out_affine):
+        self.src_shape = tuple(int(v) for v in src_shape)
+        self.out_shape = tuple(int(v) for v in out_shape)
+        self.perm = tuple(int(v) for v in perm)
+        self.flip = tuple(bool(v) for v in flip)
+        self.scale = tuple(float(v) for v in scale)
+        self.offset = tuple(float(v) for v in offset)
+        self.src_affine = np.array(src_affine, dtype=np.float64)
+        self.out_affine = np.array(out_affine, dtype=np.float64)
+        if len(self.src_shape) != 3 or len(self.out_shape) != 3 or min(self.src_shape + self.out_shape) < 1:
+            raise ValueError(f"GridPlan: shapes {self.src_shape} -> {self.out_shape} must be three positive sizes each")
+        if sorted(self.perm) != [0, 1, 2]:
+            raise ValueError(f"GridPlan: perm {self.perm} is no permutation of the axes")
+        if not all(np.isfinite(v) for v in self.scale + self.offset) or any(v == 0 for v in self.scale):
+            raise ValueError(f"GridPlan: scale {self.scale} / offset {self.offset} must be finite, scale nonzero")
+        self.tables = tuple(self._axis_tables(i) for i in range(3))
+        self._dev = {}
+
+    def source_coordinate(self, i, k):
+        """The clamped coordinate of output indices k of axis i along the (reoriented) source axis, float64."""
+        n = self.src_shape[self.perm[i]]
+        c = np.float64(self.scale[i]) * np.asarray(k, dtype=np.float64) + np.float64(self.offset[i])
+        return np.clip(c, 0.0, np.float64(n - 1))
+
+    def _axis_tables(self, i):
+        n = self.src_shape[self.perm[i]]
+        c = self.source_coordinate(i, np.arange(self.out_shape[i]))
+        i0 = np.minimum(np.floor(c), np.float64(max(n - 2, 0)))
+        frac, near = c - i0, np.rint(c)
+        if self.flip[i]:                       # the mirrored pair: its lower index is the mirror of the upper tap
+            i0 = np.float64(n - 1) - np.minimum(i0 + 1, np.float64(n - 1))
+            frac, near = 1.0 - frac, np.float64(n - 1) - near
+        return i0.astype(np.int32), frac, near.astype(np.int32)
+
+    @property
+    def identity(self):
+        return (self.src_shape == self.out_shape and self.perm == (0, 1, 2) and not any(self.flip)
+                and self.scale == (1.0, 1.0, 1.0) and self.offset == (0.0, 0.0, 0.0))
+
+    def inverse(self):
+        """The plan from this plan's output grid back onto its source grid (out_shape = src_shape): what carries a
+        prediction made on the resampled volume to the case's own voxels."""
+        perm, scale, offset = [0] * 3, [0.0] * 3, [0.0] * 3
+        for i in range(3):
+            n = self.src_shape[self.perm[i]]
+            se, oe = (-self.scale[i], (n - 1) - self.offset[i]) if self.flip[i] else (self.scale[i], self.offset[i])
+            a = self.perm[i]                   # source index j of axis a = se * k + oe  <=>  k = j / se - oe / se
+            perm[a], scale[a], offset[a] = i, 1.0 / se, 0.0 - oe / se
+        return GridPlan(self.out_shape, self.src_shape, perm, (False,) * 3, scale, offset, self.out_affine,
+                        self.src_affine)
+
+    def source_layout(self):
+        """(strides, lengths) of the source axis each output axis reads, in elements of a contiguous [C, A0, A1, A2]
+        source, and the channel stride: what the entry points take next to the tables."""
+        A = self.src_shape
+        st = (A[1] * A[2], A[2], 1)
+        return tuple(st[p] for p in self.perm), tuple(A[p] for p in self.perm), A[0] * A[1] * A[2]
+
+    def _device_tables(self, device):
+        key = (device.type, device.index)
+        if key not in self._dev:
+            self._dev[key] = tuple(tuple(torch.from_numpy(np.ascontiguousarray(t)).to(device) for t in ax)
+                                   for ax in self.tables)
+        return self._dev[key]
+
+    def apply(self, x, mode="linear"):
+        """x [A0, A1, A2] or [C, A0, A1, A2] on the device (A = src_shape) -> the same with out_shape. mode "linear":
+        fp32 or int16 in (anything else is cast to fp32 first), fp32 out, trilinear in fp64 rounded once
+        (u3d_grid_resample_linear); mode "nearest": uint8, int16, int32 or fp32, same dtype out
+        (u3d_grid_resample_nearest). An identity plan returns x itself."""
+        import ctypes
+        if mode not in ("linear", "nearest"):
+            raise ValueError(f"GridPlan.apply: mode {mode!r} (linear or nearest)")
+        if x.dim() not in (3, 4) or tuple(x.shape[-3:]) != self.src_shape or x.numel() == 0:
+            raise ValueError(f"GridPlan.apply: x {tuple(x.shape)} must be [A0, A1, A2] or [C, A0, A1, A2] with the "
+                             f"plan's source shape {self.src_shape}")
+        ops.require_device(x)
+        if self.identity:
+            return x
+        if mode == "linear" and x.dtype not in (torch.float32, torch.int16):
+            x = x.float()
+        if x.dtype not in _RS_DTYPES:
+            raise ValueError(f"GridPlan.apply: dtype {x.dtype} with mode {mode!r} (uint8, int16, int32 or float32)")
+        x = x.contiguous()
+        C = x.shape[0] if x.dim() == 4 else 1
+        st, sn, chan = self.source_layout()
+        arr_l, arr_i = ctypes.c_longlong * 3, ctypes.c_int * 3
+        strides, src_n, n_out = arr_l(*st), arr_i(*sn), arr_i(*self.out_shape)
+        out_shape = ((C,) if x.dim() == 4 else ()) + self.out_shape
+        with torch.cuda.device(x.device):
+            tabs = self._device_tables(x.device)
+            if mode == "linear":
+                out = torch.empty(out_shape, dtype=torch.float32, device=x.device)
+                call("u3d_grid_resample_linear", x.data_ptr(), _RS_DTYPES[x.dtype], C, strides, chan,
+                     src_n, n_out, *(tabs[i][0].data_ptr() for i in range(3)),
+                     *(tabs[i][1].data_ptr() for i in range(3)), out.data_ptr(), ops._stream())
+            else:
+                out = torch.empty(out_shape, dtype=x.dtype, device=x.device)
+                call("u3d_grid_resample_nearest", x.data_ptr(), _RS_DTYPES[x.dtype], C, strides, chan,
+                     src_n, n_out, *(tabs[i][2].data_ptr() for i in range(3)), out.data_ptr(), ops._stream())
+        return out
+
+
+def spacing_plan(shape, affine, pixdim=(1, 1, 2), axcodes="RAS", out_shape=None):
+    """MONAI's Orientationd(axcodes) then Spacingd(pixdim) (defaults: diagonal False, scale_extent False, padding
+    "border") of a volume [A0, A1, A2] in file index order with the 4 x 4 index-to-world affine (RAS+), as a GridPlan.
+    Orientation: output axis i takes the source axis perm[i] that runs along world axis axcodes[i], reversed (flip[i])
+    when it runs the other way; the affine becomes affine @ M, M the index map of that permutation and flip (a flipped
+    axis of length n carries the translation n - 1). Spacing, per axis of the reoriented volume: s = the column norm,
+    p = pixdim[i] (None keeps s), r = p / s, n_out = int(np.round((n - 1) * s / p + 1)) (half to even; ``out_shape``
+    overrides it), source coordinate c(k) = clip(k * r, 0, n - 1), output affine = columns scaled by r, translation kept:
+    output voxel 0 sits on reoriented voxel 0. The sampling is pinned to grid_sample's arithmetic, n_out to this closed
+    form: MONAI takes it through a matrix inverse, and where (n - 1) * s / p + 1 is a half-integer its rounding follows
+    floating-point noise; pass out_shape= to match a file it wrote."""
+    shape = tuple(int(v) for v in shape)
+    if len(shape) != 3 or min(shape) < 1:
+        raise ValueError(f"spacing_plan: shape {shape} must be three positive sizes")
+    a = _affine44(affine)
+    pix = tuple(pixdim) if np.ndim(pixdim) else (pixdim,) * 3
+    if len(pix) != 3:
+        raise ValueError(f"spacing_plan: pixdim {pixdim!r} must be one or three values")
+    for p in pix:
+        if p is not None and not (np.isfinite(p) and p > 0):
+            raise ValueError(f"spacing_plan: pixdim {pixdim!r} must be finite and positive")
+    src = orientation_of(a)
+    perm, flip = [], []
+    for w, sign in _target_orientation(axcodes):
+        ax = [i for i, (o, _) in enumerate(src) if o == w][0]
+        perm.append(ax)
+        flip.append(src[ax][1] != sign)
+    M = np.zeros((4, 4), dtype=np.float64)
+    M[3, 3] = 1
+    for i in range(3):
+        M[perm[i], i] = -1.0 if flip[i] else 1.0
+        M[perm[i], 3] = shape[perm[i]] - 1 if flip[i] else 0.0
+    re = a @ M
+    scale, n_out = [], []
+    out_affine = re.copy()
+    for i in range(3):
+        n = shape[perm[i]]
+        s = np.sqrt(np.sum(re[:3, i] * re[:3, i]))
+        p = s if pix[i] is None else np.float64(pix[i])
+        r = p / s
+        scale.append(r)
+        n_out.append(int(np.round((n - 1) * s / p + 1)))
+        out_affine[:3, i] = re[:3, i] * r
+    if out_shape is not None:
+        n_out = [int(v) for v in out_shape]
+        if len(n_out) != 3 or min(n_out) < 1:
+            raise ValueError(f"spacing_plan: out_shape {out_shape!r} must be three positive sizes")
+    return GridPlan(shape, n_out, perm, flip, scale, (0.0, 0.0, 0.0), a, out_affine)
+
+
+def resample_spacing(image, label, affine, pixdim=(1, 1, 2), axcodes="RAS"):
+    """preprocess/transforms.py:47-52 on device tensors image / label [A0, A1, A2] of one case: to ``axcodes`` and to
+    ``pixdim``, the image trilinear (fp32 out, from fp32 or int16), the label nearest (its own dtype). Returns
+    (image, label, out_affine, plan); plan.inverse() carries a prediction back."""
+    if image.shape != label.shape or image.device != label.device:
+        raise ValueError(f"resample_spacing: image {tuple(image.shape)} on {image.device}, label "
+                         f"{tuple(label.shape)} on {label.device}")
+    ops.require_device(image)
+    plan = spacing_plan(image.shape, affine, pixdim, axcodes)
+    img = plan.apply(image, "linear")
+    return (img if img.dtype == torch.float32 else img.float()), plan.apply(label, "nearest"), plan.out_affine, plan
+
+
+def preprocess_case(image, label, affine, cid, pixdim=(1, 1, 2), axcodes="RAS", min_filter=1e6, min_filter_up=1e5):
+    """preprocess/forward_crop.py:121-207 for one case on the device: resample_spacing, then body_crop (which clears the
+    label codes >= 14). Returns body_crop's (image_a, label_a, info); info gains ``affine`` (of the resampled grid,
+    before the crops), ``spacing`` (= pixdim) and ``plan``."""
+    img, lab, out_affine, plan = resample_spacing(image, label, affine, pixdim, axcodes)
+    image_a, label_a, info = body_crop(img, lab, cid, min_filter, min_filter_up)
+    info.update(affine=out_affine, spacing=tuple(pixdim) if np.ndim(pixdim) else (pixdim,) * 3, plan=plan)
+    return image_a, label_a, info
