@@ -6,8 +6,9 @@ through u3d._lib.call with the argument lists of u3d/ops.py, on buffers the test
 is pre-filled with NaN bit patterns, has exactly the advertised size and is followed by a guard block that must come
 back unchanged; zeroed counter words must come back zero. Every element is compared; none is excluded.
 
-Out of scope (the next pass): the stem (stem.hip), the streaming head (head.hip), the upsample kernels and the fused
-forms, which are pinned BITWISE to the plain launches tested here (see the table below).
+Out of scope here: the stem (stem.hip), the streaming head (head.hip), the upsample kernels and the helpers of misc.hip
+are pinned the same way by test_gpu_trunk_edge.py; the fused forms are pinned BITWISE to the plain launches tested here
+(see the table below).
 
 BOUNDS, per element, each from the arithmetic and none from a measured result:
 
@@ -117,66 +118,11 @@ import torch
 import conv_cases as cc
 import conv_reference as cr
 from conv_reference import BF, F32
+from gpu_buffers import Bufs as _Bufs, opts as _opts, ptr as _ptr
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 256            # bytes after each output / workspace
-GUARD_BYTE = 0xA5
 TWO_ROUNDINGS = ("u3d_conv32_ring", "u3d_conv32_ring_q", "u3d_conv32_brick", "u3d_convg_brick")
-
-
-class _Bufs:
-    """Exact-size device buffers, each followed by a guard block; ``check`` after the launch."""
-
-    def __init__(self, dev):
-        self.dev, self.all = dev, []
-
-    def _new(self, nbytes, fill, zero):
-        buf = torch.full((nbytes + GUARD,), fill, dtype=torch.uint8, device=self.dev)
-        buf[nbytes:] = GUARD_BYTE
-        self.all.append((buf, nbytes, zero))
-        return buf
-
-    def nan(self, shape, dtype):
-        """A tensor of NaN bit patterns (0xFF bytes: a NaN in bf16 and in fp32) of exactly this shape."""
-        numel = 1
-        for s in shape:
-            numel *= s
-        nbytes = numel * (2 if dtype == BF else 4)
-        return self._new(nbytes, 0xFF, False)[:nbytes].view(dtype).view(shape)
-
-    def ws(self, nbytes):
-        """A workspace of exactly nbytes of NaN bit patterns; its data pointer (None for 0 bytes)."""
-        return self._new(nbytes, 0xFF, False).data_ptr() if nbytes > 0 else None
-
-    def zeros(self, nbytes):
-        """Zeroed counter / claim words, which every launch must leave zero."""
-        return self._new(nbytes, 0, True).data_ptr()
-
-    def check(self):
-        for buf, nbytes, zero in self.all:
-            assert bool((buf[nbytes:] == GUARD_BYTE).all()), "the kernel wrote past a buffer"
-            if zero:
-                assert not bool(buf[:nbytes].any()), "counter words not left zero"
-
-
-class _opts:
-    def __init__(self, opts):
-        self.opts = opts
-
-    def __enter__(self):
-        from u3d import ops
-        self.cms = [ops.option(k, v) for k, v in self.opts]
-        for cm in self.cms:
-            cm.__enter__()
-
-    def __exit__(self, *a):
-        for cm in reversed(self.cms):
-            cm.__exit__(*a)
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
 
 
 def _operands(c, dev):
