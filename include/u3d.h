@@ -779,6 +779,19 @@ int u3d_mask_window_axis(const unsigned char* in, unsigned char* out, long long 
                          int hi, int op, const int* gate, u3d_stream_t stream);
 int u3d_nonzero_bbox(const void* x, int dtype, int Z, int Y, int X, int* record, int accumulate, const int* gate,
                      u3d_stream_t stream);
+/* u3d_ccl_keep_largest: the per-organ cleanup of a label map in one labelling. codes uint8 [Z][Y][X]; a voxel joins a
+ * face neighbour only when both hold the same code in 1..num_labels (1 <= num_labels <= 255). Per label the component
+ * with the most voxels is kept, on a tie the one whose first voxel comes first in C order; every other voxel of that
+ * label becomes 0. Code 0 and codes above num_labels are copied unchanged. out may be codes itself. record, device
+ * int32 [num_labels][U3D_KEEP_RECORD], for label l at record[l - 1]:
+ *   {components, voxels, kept voxels, linear index of the kept component's first voxel (-1 when the label is absent)}
+ * Sizes and the selection keys (size << 32 | INT_MAX - root, one 64-bit atomic max per component) are integers, so the
+ * result is a pure function of codes. No host read. Z * Y * X < 2^31. ws: u3d_ccl_keep_largest_ws_bytes(V) bytes
+ * (-1 for V < 1 or V >= 2^31; 8 bytes per voxel and a table), contents undefined on entry and exit. */
+#define U3D_KEEP_RECORD 4
+long long u3d_ccl_keep_largest_ws_bytes(long long V);
+int u3d_ccl_keep_largest(const unsigned char* codes, int Z, int Y, int X, int num_labels, unsigned char* out,
+                         int* record, void* ws, u3d_stream_t stream);
 
 /* ---------------------------------------------------------------- distance transform, surface metrics (csrc/edt.hip)
  * Volumes are [Z][Y][X]; spacing (sz, sy, sx) in the same order. Additive: no reference line (u3d/surface.py).
@@ -844,6 +857,16 @@ int u3d_grid_resample_linear(const void* src, int src_dtype, int C, const long l
 int u3d_grid_resample_nearest(const void* src, int src_dtype, int C, const long long* src_stride,
                               long long src_chan_stride, const int* src_n, const int* n_out, const int* near_0,
                               const int* near_1, const int* near_2, void* out, u3d_stream_t stream);
+/* u3d_grid_resample_argmax: src fp32 with C channels (1 <= C <= 256) -> out uint8 [n_out[0]][n_out[1]][n_out[2]], the
+ * channel whose trilinear value (as u3d_grid_resample_linear forms it: fp64, rounded once to fp32) is largest; ties go
+ * to the lowest channel, a NaN counts as the maximum and the first NaN wins (torch.argmax). Equal, bit for bit, to the
+ * argmax over u3d_grid_resample_linear's output, which is never formed. An output voxel with an index outside
+ * [valid_lo[a], valid_hi[a]) on any axis (host arrays of 3; an empty range is allowed) gets 0; a row outside on axis 0
+ * or 1 reads nothing. */
+int u3d_grid_resample_argmax(const float* src, int C, const long long* src_stride, long long src_chan_stride,
+                             const int* src_n, const int* n_out, const int* i0_0, const int* i0_1, const int* i0_2,
+                             const double* frac_0, const double* frac_1, const double* frac_2, const int* valid_lo,
+                             const int* valid_hi, unsigned char* out, u3d_stream_t stream);
 
 /* ---------------------------------------------------------------- style discriminators (csrc/disc.hip)
  * get_style_discriminator_output (unet3D.py:1832-1849), deep_style_discriminator_output (:1852-1905),

@@ -19,6 +19,13 @@
 //  * ccl_pick_kernel          the largest label with size >= min_filter, the earliest on a tie; the record.
 //  * bbox_kernel<.., SELECT>  the uint8 mask of the chosen label and its bounding box: block-reduced in LDS, one
 //                             atomic min / max per block and bound.
+// Per-label largest component (u3d_ccl_keep_largest), one labelling for all the organs of a label map:
+//  * keep_local_kernel / keep_seam_kernel   the two kernels above with the voxel's code next to its parent: a voxel
+//                             joins a predecessor only when both hold the same code in 1..num_labels.
+//  * keep_flatten_sizes_kernel  parent[v] = root and sizes[root] += run lengths (integer adds: no arrival order).
+//  * keep_best_kernel         per label an atomic max over its roots of (size << 32) | (INT_MAX - root): the largest,
+//                             the earliest on a tie; block-reduced in LDS.
+//  * keep_filter_kernel       out = code where parent == the label's best root, 0 otherwise; the record.
 // Mask helpers: body_threshold_kernel (vol > t, optionally the 2x2x2 erosion in the same pass), mask_window_kernel
 // (AND / OR over a window along one axis), bbox_kernel<.., NONZERO> (bounding box and count of the nonzero voxels).
 // The helpers take a gate: a device int that, when nonzero, turns the launch into a no-op, so that the fallback route
@@ -298,6 +305,142 @@ __global__ __launch_bounds__(CB) void mask_window_kernel(const unsigned char* __
   }
 }
 
+// ---- per-label largest component (u3d_ccl_keep_largest): one labelling of the whole code map, a voxel joining only
+// neighbours of its own code, then per root its size, per label the best (size, earliest root) and a filter.
+constexpr int KL = 256;  // table rows: the codes a uint8 holds
+
+// the table behind the parents and the sizes in the workspace
+struct KeepTable {
+  unsigned long long best[KL];  // per label max over its roots of (size << 32) | (INT_MAX - root); 0: label absent
+  int ncomp[KL], nvox[KL];
+};
+
+__device__ __forceinline__ bool keep_takes_part(unsigned char c, int num_labels) { return c != 0 && c <= num_labels; }
+
+// ccl_local_kernel with the tile's codes next to its parents; also clears the sizes of the tile's voxels
+__global__ __launch_bounds__(CB) void keep_local_kernel(const unsigned char* codes, int Z, int Y, int X, int ntx,
+                                                        int nty, int num_labels, int* __restrict__ parent,
+                                                        int* __restrict__ sizes) {
+  __shared__ int lp[TILE];
+  __shared__ unsigned char lc[TILE];
+  const int t = blockIdx.x;
+  const int x0 = (t % ntx) * TX, y0 = ((t / ntx) % nty) * TY, z0 = (t / (ntx * nty)) * TZ;
+  for (int l = threadIdx.x; l < TILE; l += CB) {
+    const int x = x0 + l % TX, y = y0 + (l / TX) % TY, z = z0 + l / (TX * TY);
+    unsigned char c = 0;
+    if (x < X && y < Y && z < Z) c = codes[((long long)z * Y + y) * X + x];
+    if (!keep_takes_part(c, num_labels)) c = 0;
+    lc[l] = c;
+    lp[l] = c ? l : -1;
+  }
+  __syncthreads();
+  for (int l = threadIdx.x; l < TILE; l += CB) local_unite_codes(lp, lc, l, l % TX, (l / TX) % TY, l / (TX * TY));
+  __syncthreads();
+  for (int l = threadIdx.x; l < TILE; l += CB) {
+    const int x = x0 + l % TX, y = y0 + (l / TX) % TY, z = z0 + l / (TX * TY);
+    if (x < X && y < Y && z < Z) {
+      const long long v = ((long long)z * Y + y) * X + x;
+      parent[v] = local_result(lp, l, z0, y0, x0, Y, X);
+      sizes[v] = 0;
+    }
+  }
+}
+
+// ccl_seam_kernel on codes
+__global__ __launch_bounds__(CROW) void keep_seam_kernel(const unsigned char* codes, int Z, int Y, int X,
+                                                         int* __restrict__ parent) {
+  const long long rows = (long long)Z * Y;
+  for (long long r = blockIdx.x; r < rows; r += gridDim.x) {
+    const int z = (int)(r / Y), y = (int)(r - (long long)z * Y);
+    const bool face = (y > 0 && y % TY == 0) || (z > 0 && z % TZ == 0);
+    const int step = face ? 1 : TX;
+    for (int x = face ? threadIdx.x : TX * (1 + threadIdx.x); x < X; x += step * CROW)
+      seam_unite_codes(parent, codes, (int)(r * X + x), z, y, x, Y, X);
+  }
+}
+
+// parent[v] = root, sizes[root] += the voxels below it and nvox[code] += the voxels of the code: each thread walks 8
+// consecutive voxels and adds a run's length when the root changes (a run has one code); the codes through an LDS table
+__global__ __launch_bounds__(CB) void keep_flatten_sizes_kernel(const unsigned char* codes, int V,
+                                                                int* __restrict__ parent, int* __restrict__ sizes,
+                                                                KeepTable* __restrict__ tab) {
+  __shared__ int h[KL];
+  for (int j = threadIdx.x; j < KL; j += CB) h[j] = 0;
+  __syncthreads();
+  for (long long i0 = (blockIdx.x * (long long)CB + threadIdx.x) * 8; i0 < V; i0 += (long long)gridDim.x * CB * 8) {
+    int cur = -1, cnt = 0;
+    for (int k = 0; k < 8 && i0 + k < V; ++k) {
+      const int i = (int)(i0 + k);
+      flatten(parent, i);
+      const int r = load<AGENT>(parent + i);  // this thread's own store, or a root's own index, or -1
+      if (r != cur) {
+        if (cnt && cur >= 0) {
+          atomicAdd(&sizes[cur], cnt);
+          atomicAdd(&h[codes[cur]], cnt);
+        }
+        cur = r;
+        cnt = 0;
+      }
+      ++cnt;
+    }
+    if (cnt && cur >= 0) {
+      atomicAdd(&sizes[cur], cnt);
+      atomicAdd(&h[codes[cur]], cnt);
+    }
+  }
+  __syncthreads();
+  for (int j = threadIdx.x; j < KL; j += CB)
+    if (h[j]) atomicAdd(&tab->nvox[j], h[j]);
+}
+
+// per label the best key over its roots and the number of roots: block-reduced in LDS, one atomic per block and label
+__global__ __launch_bounds__(CB) void keep_best_kernel(const unsigned char* codes, int V,
+                                                       const int* __restrict__ parent, const int* __restrict__ sizes,
+                                                       KeepTable* __restrict__ tab) {
+  __shared__ unsigned long long b[KL];
+  __shared__ int n[KL];
+  for (int j = threadIdx.x; j < KL; j += CB) b[j] = 0, n[j] = 0;
+  __syncthreads();
+  for (long long i = blockIdx.x * (long long)CB + threadIdx.x; i < V; i += (long long)gridDim.x * CB) {
+    if (parent[i] != (int)i) continue;
+    const unsigned long long key = ((unsigned long long)(unsigned)sizes[i] << 32) | (unsigned)(INT_MAX - (int)i);
+    const int c = codes[i];
+    atomicMax(&b[c], key);
+    atomicAdd(&n[c], 1);
+  }
+  __syncthreads();
+  for (int j = threadIdx.x; j < KL; j += CB)
+    if (n[j]) {
+      atomicMax(&tab->best[j], b[j]);
+      atomicAdd(&tab->ncomp[j], n[j]);
+    }
+}
+
+// out = codes where the voxel takes no part or hangs below its label's best root, 0 otherwise; block 0 writes the record
+__global__ __launch_bounds__(CB) void keep_filter_kernel(const unsigned char* codes, int V,
+                                                         const int* __restrict__ parent,
+                                                         const KeepTable* __restrict__ tab, int num_labels,
+                                                         unsigned char* out, int* __restrict__ record) {
+  __shared__ int root[KL];
+  for (int j = threadIdx.x; j < KL; j += CB) {
+    const unsigned long long k = tab->best[j];
+    root[j] = k ? INT_MAX - (int)(unsigned)(k & 0xffffffffu) : -1;
+    if (blockIdx.x == 0 && j >= 1 && j <= num_labels) {
+      int* rec = record + (j - 1) * U3D_KEEP_RECORD;
+      rec[0] = tab->ncomp[j];
+      rec[1] = tab->nvox[j];
+      rec[2] = (int)(k >> 32);
+      rec[3] = root[j];
+    }
+  }
+  __syncthreads();
+  for (long long i = blockIdx.x * (long long)CB + threadIdx.x; i < V; i += (long long)gridDim.x * CB) {
+    const unsigned char c = codes[i];
+    const int p = parent[i];
+    out[i] = (p < 0 || p == root[c]) ? c : 0;
+  }
+}
+
 static inline int row_blocks(long long rows) { return (int)std::min<long long>(CMAXB, std::max<long long>(1, rows)); }
 static inline long long chunks(long long V) { return (V + CH - 1) / CH; }
 
@@ -358,6 +501,40 @@ extern "C" int u3d_ccl_select(const int* labels, int Z, int Y, int X, const int*
   hipLaunchKernelGGL((bbox_kernel<int, SELECT>), dim3(row_blocks((long long)Z * Y)), dim3(CROW), 0, s, labels, Z, Y, X,
                      mask_out, record, (const int*)nullptr);
   return check_launch("ccl_select");
+}
+
+// parents [V] int32, sizes [V] int32, then the table
+extern "C" long long u3d_ccl_keep_largest_ws_bytes(long long V) {
+  if (V < 1 || V >= (1LL << 31)) return -1;
+  return 8 * V + (long long)sizeof(KeepTable);
+}
+
+extern "C" int u3d_ccl_keep_largest(const unsigned char* codes, int Z, int Y, int X, int num_labels,
+                                    unsigned char* out, int* record, void* ws, u3d_stream_t stream) {
+  U3D_REQUIRE(Z >= 1 && Y >= 1 && X >= 1, "ccl_keep_largest: bad shape %d x %d x %d", Z, Y, X);
+  const long long V = (long long)Z * Y * X;
+  U3D_REQUIRE(V < (1LL << 31), "ccl_keep_largest: %lld voxels: the parents are int32 (V < 2^31)", V);
+  U3D_REQUIRE(num_labels >= 1 && num_labels < KL, "ccl_keep_largest: num_labels=%d (1..%d)", num_labels, KL - 1);
+  U3D_REQUIRE(codes && out && record && ws, "ccl_keep_largest: null pointer");
+  U3D_REQUIRE(((uintptr_t)ws & 7) == 0, "ccl_keep_largest: the workspace must be 8-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  int* parent = (int*)ws;
+  int* sizes = parent + V;
+  KeepTable* tab = (KeepTable*)(sizes + V);
+  U3D_HIP(hipMemsetAsync(tab, 0, sizeof(KeepTable), s));
+  const int ntx = cdiv(X, TX), nty = cdiv(Y, TY), ntz = cdiv(Z, TZ);
+  const long long tiles = (long long)ntx * nty * ntz;  // <= V: fits the grid's x
+  const int gb8 = (int)std::min<long long>(CMAXB, (V + CB * 8 - 1) / (CB * 8));
+  const int gb = (int)std::min<long long>(CMAXB, (V + CB - 1) / CB);
+  hipLaunchKernelGGL(keep_local_kernel, dim3((unsigned)tiles), dim3(CB), 0, s, codes, Z, Y, X, ntx, nty, num_labels,
+                     parent, sizes);
+  hipLaunchKernelGGL(keep_seam_kernel, dim3(row_blocks((long long)Z * Y)), dim3(CROW), 0, s, codes, Z, Y, X, parent);
+  hipLaunchKernelGGL(keep_flatten_sizes_kernel, dim3(gb8), dim3(CB), 0, s, codes, (int)V, parent, sizes, tab);
+  hipLaunchKernelGGL(keep_best_kernel, dim3(gb), dim3(CB), 0, s, codes, (int)V, (const int*)parent,
+                     (const int*)sizes, tab);
+  hipLaunchKernelGGL(keep_filter_kernel, dim3(gb), dim3(CB), 0, s, codes, (int)V, (const int*)parent,
+                     (const KeepTable*)tab, num_labels, out, record);
+  return check_launch("ccl_keep_largest");
 }
 
 extern "C" int u3d_body_threshold(const float* vol, int Z, int Y, int X, float t, int erode, unsigned char* out,

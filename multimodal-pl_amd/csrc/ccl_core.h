@@ -125,6 +125,28 @@ CCL_HD void seam_unite(int* parent, int v, int z, int y, int x, int Y, int X) {
   if (z > 0 && z % TZ == 0 && load<AGENT>(parent + v - X * Y) >= 0) unite<AGENT>(parent, v, v - X * Y);
 }
 
+// Multi-label forms (u3d_ccl_keep_largest): a voxel carries a code, 0 for a voxel that takes no part (its parent is
+// -1), and joins a predecessor only when both hold the same nonzero code. The unions are the ones above, so the
+// invariants hold unchanged and a component's root is still its smallest linear index; flatten is shared.
+// Tile-local phase, one voxel: lc[TILE] are the codes of the tile next to its parents lp[TILE].
+CCL_HD void local_unite_codes(int* lp, const unsigned char* lc, int l, int lx, int ly, int lz) {
+  const unsigned char c = lc[l];
+  if (c == 0) return;
+  if (lx > 0 && lc[l - 1] == c) unite<WORKGROUP>(lp, l, l - 1);
+  if (ly > 0 && lc[l - TX] == c) unite<WORKGROUP>(lp, l, l - TX);
+  if (lz > 0 && lc[l - TX * TY] == c) unite<WORKGROUP>(lp, l, l - TX * TY);
+}
+
+// seam phase, one voxel: codes[] is the volume as given; a voxel takes part when its parent is not -1, and a
+// predecessor with the same code then takes part too
+CCL_HD void seam_unite_codes(int* parent, const unsigned char* codes, int v, int z, int y, int x, int Y, int X) {
+  if (load<AGENT>(parent + v) < 0) return;
+  const unsigned char c = codes[v];
+  if (x > 0 && x % TX == 0 && codes[v - 1] == c) unite<AGENT>(parent, v, v - 1);
+  if (y > 0 && y % TY == 0 && codes[v - X] == c) unite<AGENT>(parent, v, v - X);
+  if (z > 0 && z % TZ == 0 && codes[v - X * Y] == c) unite<AGENT>(parent, v, v - X * Y);
+}
+
 // flatten, one voxel: parent[v] = its root. Returns 1 when v is a root. Safe next to concurrent flattens: a voxel's
 // parent only moves to an ancestor, and roots never change once the unions are complete.
 CCL_HD int flatten(int* parent, int v) {

@@ -10,6 +10,10 @@
 // its two weights are uniform (scalar loads of the tables); each lane forms its two column offsets and its weight
 // once and walks the channels. When the source's contiguous axis is output axis 2 (no permutation: the AMOS case)
 // adjacent lanes read adjacent or equal elements of four source rows and store one contiguous output row.
+//
+// The way back for scores, grid_resample_argmax_kernel: the same row shape, but a lane keeps only the index of the
+// channel whose trilinear value is largest (rs::argmax_trilinear: the linear kernel's arithmetic and rounding, so the
+// argmax over its output bit for bit) and stores one byte; voxels outside a box of valid output indices get 0.
 #include "common.h"
 #include "resample_core.h"
 
@@ -72,6 +76,38 @@ __global__ __launch_bounds__(RS_NT) void grid_resample_nearest_kernel(const T* _
   for (int k2 = threadIdx.x & (lanes - 1); k2 < n2; k2 += lanes) {
     const long long o = base + rs::nearest_offset(tab.idx[2][k2], ax.n_src[2], ax.stride[2]);
     for (int c = 0; c < C; ++c) orow[c * plane + k2] = src[c * cstride + o];
+  }
+}
+
+struct RsValid {
+  int lo[3], hi[3];
+};
+
+// out uint8 = the argmax over the channels of what grid_resample_linear_kernel<float> would store, 0 outside the valid
+// box. The same row shape: a row outside the box on axis 0 or 1 (wave-uniform) is zeros and reads no table and no source.
+__global__ __launch_bounds__(RS_NT) void grid_resample_argmax_kernel(const float* __restrict__ src, int C,
+                                                                    long long cstride, RsAxes ax, RsTables tab,
+                                                                    RsValid valid, unsigned char* __restrict__ out,
+                                                                    int shift, int rows) {
+  const int row = rs_row(shift, rows);
+  if (row < 0) return;
+  const int k0 = row / ax.n_out[1], k1 = row - k0 * ax.n_out[1];
+  const int n2 = ax.n_out[2], lanes = 1 << shift;
+  unsigned char* orow = out + (long long)row * n2;
+  if (k0 < valid.lo[0] || k0 >= valid.hi[0] || k1 < valid.lo[1] || k1 >= valid.hi[1]) {
+    for (int k2 = threadIdx.x & (lanes - 1); k2 < n2; k2 += lanes) orow[k2] = 0;
+    return;
+  }
+  const rs::Pair p0 = rs::pair_offsets(tab.idx[0][k0], ax.n_src[0], ax.stride[0]);
+  const rs::Pair p1 = rs::pair_offsets(tab.idx[1][k1], ax.n_src[1], ax.stride[1]);
+  const double f0 = tab.frac[0][k0], f1 = tab.frac[1][k1];
+  for (int k2 = threadIdx.x & (lanes - 1); k2 < n2; k2 += lanes) {
+    int best = 0;
+    if (k2 >= valid.lo[2] && k2 < valid.hi[2]) {
+      const rs::Pair p2 = rs::pair_offsets(tab.idx[2][k2], ax.n_src[2], ax.stride[2]);
+      best = rs::argmax_trilinear(src, C, cstride, p0, p1, p2, f0, f1, tab.frac[2][k2]);
+    }
+    orow[k2] = (unsigned char)best;
   }
 }
 
@@ -151,4 +187,29 @@ extern "C" int u3d_grid_resample_nearest(const void* src, int src_dtype, int C, 
     hipLaunchKernelGGL(grid_resample_nearest_kernel<uint32_t>, dim3(blocks), dim3(RS_NT), 0, s, (const uint32_t*)src, C,
                        src_chan_stride, ax, tab, (uint32_t*)out, shift, rows);
   return check_launch("grid_resample_nearest_kernel");
+}
+
+extern "C" int u3d_grid_resample_argmax(const float* src, int C, const long long* src_stride, long long src_chan_stride,
+                                        const int* src_n, const int* n_out, const int* i0_0, const int* i0_1,
+                                        const int* i0_2, const double* frac_0, const double* frac_1,
+                                        const double* frac_2, const int* valid_lo, const int* valid_hi,
+                                        unsigned char* out, u3d_stream_t stream) {
+  U3D_REQUIRE(C <= 256, "grid_resample_argmax: C=%d (1..256: the result is a uint8)", C);
+  U3D_REQUIRE(i0_0 && i0_1 && i0_2 && frac_0 && frac_1 && frac_2, "grid_resample_argmax: null table");
+  U3D_REQUIRE(valid_lo && valid_hi, "grid_resample_argmax: null valid range");
+  RsAxes ax;
+  int rows, shift;
+  unsigned blocks;
+  int rc = rs_geometry("grid_resample_argmax", src, out, C, src_stride, src_chan_stride, src_n, n_out, ax, rows, shift,
+                       blocks);
+  if (rc) return rc;
+  RsValid valid;
+  for (int i = 0; i < 3; ++i) {
+    valid.lo[i] = valid_lo[i];
+    valid.hi[i] = valid_hi[i];
+  }
+  const RsTables tab{{i0_0, i0_1, i0_2}, {frac_0, frac_1, frac_2}};
+  hipLaunchKernelGGL(grid_resample_argmax_kernel, dim3(blocks), dim3(RS_NT), 0, (hipStream_t)stream, src, C,
+                     src_chan_stride, ax, tab, valid, out, shift, rows);
+  return check_launch("grid_resample_argmax_kernel");
 }

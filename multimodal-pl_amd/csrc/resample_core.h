@@ -56,5 +56,22 @@ RS_HD double trilinear(const T* src, Pair p0, Pair p1, Pair p2, double f0, doubl
   return lerp(lerp(v00, v01, f1), lerp(v10, v11, f1), f0);
 }
 
+// the channel, of C channels cstride elements apart, whose trilinear value rounded to fp32 is largest: the lowest
+// channel on a tie, and a NaN counts as the maximum with the first NaN winning (torch.argmax's rule). Each channel is
+// evaluated by trilinear as the linear kernel evaluates it, so this is the argmax over that kernel's output.
+RS_HD int argmax_trilinear(const float* src, int C, long long cstride, Pair p0, Pair p1, Pair p2, double f0, double f1,
+                           double f2) {
+  int best = 0;
+  float bv = (float)trilinear(src, p0, p1, p2, f0, f1, f2);
+  for (int c = 1; c < C; ++c) {
+    const float v = (float)trilinear(src + c * cstride, p0, p1, p2, f0, f1, f2);
+    if (bv == bv && (v > bv || v != v)) {  // once bv is a NaN nothing replaces it
+      bv = v;
+      best = c;
+    }
+  }
+  return best;
+}
+
 }  // namespace rs
 }  // namespace u3d

@@ -165,6 +165,8 @@ _SIGS = {
     "u3d_body_threshold": [P, I, I, I, F, I, P, P, P],
     "u3d_mask_window_axis": [P, P, L, I, L, I, I, I, P, P],
     "u3d_nonzero_bbox": [P, I, I, I, I, P, I, P, P],
+    "u3d_ccl_keep_largest_ws_bytes": [L],
+    "u3d_ccl_keep_largest": [P, I, I, I, I, P, P, P, P],
     "u3d_edt_max_extent": [],
     "u3d_edt_tile": [P, P],
     "u3d_edt_ws_bytes": [L],
@@ -175,6 +177,7 @@ _SIGS = {
     "u3d_surface_dist_reduce": [P, P, L, D, P, P, P],
     "u3d_grid_resample_linear": [P, I, I, P, L, P, P, P, P, P, P, P, P, P, P],
     "u3d_grid_resample_nearest": [P, I, I, P, L, P, P, P, P, P, P, P],
+    "u3d_grid_resample_argmax": [P, I, P, L, P, P, P, P, P, P, P, P, P, P, P, P],
     "u3d_disc_conv_fwd_splits": [I, I, I, I, I, I],
     "u3d_disc_conv_fwd_ws_bytes": [I, I, I, I, I, I],
     "u3d_disc_conv_fwd": [I, P, I, I, I, I, I, I, I, P, P, P, I, I, I, I, P, P],
@@ -198,7 +201,7 @@ _RESTYPE = {"u3d_stem_fwd_ws_bytes": L, "u3d_stem1_stats_ws_floats": L, "u3d_con
             "u3d_consistency_ws_bytes": L, "u3d_volume_stats_ws_bytes": L, "u3d_convg_brick_stats_ws_floats": L,
             "u3d_deepsup_loss_workspace_bytes": L, "u3d_loss_ps_workspace_bytes": L,
             "u3d_deepsup_loss_ps_workspace_bytes": L, "u3d_disc_conv_fwd_ws_bytes": L, "u3d_disc_conv_wgrad_ws_bytes": L,
-            "u3d_atlas_build_ws_bytes": L, "u3d_ccl_ws_bytes": L, "u3d_ccl_select_ws_bytes": L, "u3d_edt_ws_bytes": L,
+            "u3d_atlas_build_ws_bytes": L, "u3d_ccl_ws_bytes": L, "u3d_ccl_select_ws_bytes": L, "u3d_ccl_keep_largest_ws_bytes": L, "u3d_edt_ws_bytes": L,
             "u3d_surface_reduce_ws_bytes": L, "u3d_disc_bias_grad_ws_bytes": L, "u3d_disc_first_wgrad_ws_bytes": L, "u3d_disc_side_wgrad_ws_bytes": L}
 
 _lib = None

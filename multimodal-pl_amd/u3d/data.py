@@ -30,6 +30,12 @@
   border clamping, or nearest). monai is not installed here: the sampling is pinned to torch's grid_sample on float64
   (the engine MONAI calls) and to scipy's map_coordinates, the output grid to its formulas; bit parity with one MONAI
   release is not pinned, in particular the output size where (n - 1) s / p + 1 is a half-integer (``out_shape=``).
+* ``restore_prediction`` / ``GridPlan.restrict_source`` / ``GridPlan.apply_argmax`` / ``keep_largest_per_label``: from
+  the network's output on preprocess_case's image_a to a uint8 label map on the case's own voxels. body_crop records
+  where its crop sits (``origin``, ``input_shape``); the inverse plan is restricted to that crop and the scores are
+  interpolated and decided in one kernel (u3d_grid_resample_argmax: the argmax over the linear kernel's output, bit
+  for bit, without the C resampled volumes); the per-organ largest-component cleanup labels all organs at once
+  (u3d_ccl_keep_largest: the union-find of csrc/ccl.hip joining only voxels of one code). No host read in either.
 """
 import math
 
@@ -467,13 +473,16 @@ def body_crop(image, label, cid, min_filter=1e6, min_filter_up=1e5):
     Returns (image_a, label_a, info): slices of image and of the cleared label; info holds label_range, bbox, bbox_up
     (min, inclusive max), size, size_up, route, route_up (ROUTE_COMPONENT / ROUTE_FALLBACK), inter_all, inter_up,
     found_hand, mask (the body mask as the reference leaves it), label_sum_before / _after (0-dim device tensors: the
-    reference's consistency print). Three host reads: the label range and the two body records. An empty label or an
+    reference's consistency print), origin ((z, y, x) of image_a[0, 0, 0] in the volume passed in: the three nested
+    crops added up) and input_shape (that volume's shape): what restore_prediction needs to undo the crop. Three host
+    reads: the label range and the two body records. An empty label or an
     empty body raises ValueError."""
     _volume3(image, "body_crop")
     _volume3(label, "body_crop")
     if image.shape != label.shape or image.device != label.device:
         raise ValueError(f"body_crop: image {tuple(image.shape)} on {image.device}, label {tuple(label.shape)} on "
                          f"{label.device}")
+    input_shape = tuple(image.shape)
     with torch.cuda.device(image.device):
         label = torch.where(label >= 14, torch.zeros((), dtype=label.dtype, device=label.device), label)
         sum_before = label.double().sum()
@@ -505,6 +514,7 @@ def body_crop(image, label, cid, min_filter=1e6, min_filter_up=1e5):
                 "route": ROUTE_COMPONENT if r["found"] else ROUTE_FALLBACK,
                 "route_up": ROUTE_COMPONENT if u["found"] else ROUTE_FALLBACK,
                 "inter_all": inter_all, "inter_up": inter_up, "found_hand": bool(hand), "mask": mask,
+                "origin": (zmin + (zmin_up if hand else 0), ymin, xmin + x0), "input_shape": input_shape,
                 "label_sum_before": sum_before, "label_sum_after": label_a.double().sum()}
         return image_a, label_a, info
 
@@ -682,6 +692,68 @@ class GridPlan:
                      src_n, n_out, *(tabs[i][2].data_ptr() for i in range(3)), out.data_ptr(), ops._stream())
         return out
 
+    def restrict_source(self, origin, shape):
+        """(plan_w, valid) for a source of which only the box [origin, origin + shape) exists, as a contiguous crop:
+        plan_w reads that crop (src_shape = shape, the same perm and scale, offset[i] - origin[perm[i]]); valid[i] =
+        (lo, hi), the output indices of axis i whose nearest source index in THIS plan (the near table: rint of the
+        clamped coordinate) lies inside the box; coordinates are monotone, so it is one range, (0, 0) when empty. The
+        range is taken from this plan's table, not from plan_w's: rint(c - o) is not rint(c) - o for a half-integer c
+        and an odd o (half to even). For a plan without flips (an inverse plan has none); ValueError otherwise, or
+        when the box is not inside src_shape."""
+        origin, shape = tuple(int(v) for v in origin), tuple(int(v) for v in shape)
+        if any(self.flip):
+            raise ValueError(f"GridPlan.restrict_source: the plan flips {self.flip}; restrict a plan without flips")
+        if len(origin) != 3 or len(shape) != 3 or any(
+                o < 0 or s < 1 or o + s > n for o, s, n in zip(origin, shape, self.src_shape)):
+            raise ValueError(f"GridPlan.restrict_source: the box at {origin} of shape {shape} is not inside the "
+                             f"source {self.src_shape}")
+        src_affine = self.src_affine.copy()
+        src_affine[:3, 3] += self.src_affine[:3, :3] @ np.array(origin, dtype=np.float64)
+        plan_w = GridPlan(shape, self.out_shape, self.perm, self.flip, self.scale,
+                          tuple(self.offset[i] - origin[self.perm[i]] for i in range(3)), src_affine, self.out_affine)
+        valid = []
+        for i in range(3):
+            a = self.perm[i]
+            near = self.tables[i][2]
+            inside = np.flatnonzero((near >= origin[a]) & (near < origin[a] + shape[a]))
+            valid.append((int(inside[0]), int(inside[-1]) + 1) if inside.size else (0, 0))
+        return plan_w, tuple(valid)
+
+    def apply_argmax(self, x, valid=None):
+        """x [C, A0, A1, A2] float on the device (A = src_shape, 1 <= C <= 256) -> uint8 [out_shape]: the argmax over
+        the channels of apply(x, "linear"), bit for bit (ties to the lowest channel, a NaN is the maximum, the first
+        wins), without forming the C resampled volumes (u3d_grid_resample_argmax). valid: per output axis (lo, hi); a
+        voxel with an index outside a range gets 0 (default: everything is valid). x is read through its own strides:
+        a permuted view costs no copy (zero strides are made contiguous first); dtypes other than fp32 are cast. An
+        identity plan runs the same kernel with all weights 0: the plain channel argmax of finite values."""
+        import ctypes
+        if x.dim() != 4 or tuple(x.shape[1:]) != self.src_shape or not 1 <= x.shape[0] <= 256:
+            raise ValueError(f"GridPlan.apply_argmax: x {tuple(x.shape)} must be [C, A0, A1, A2] with 1 <= C <= 256 and "
+                             f"the plan's source shape {self.src_shape}")
+        if not x.dtype.is_floating_point:
+            raise ValueError(f"GridPlan.apply_argmax: dtype {x.dtype} (a float tensor of scores is needed)")
+        ops.require_device(x)
+        valid = tuple((0, n) for n in self.out_shape) if valid is None else tuple(
+            (int(lo), int(hi)) for lo, hi in valid)
+        if len(valid) != 3:
+            raise ValueError(f"GridPlan.apply_argmax: valid {valid!r} must hold one (lo, hi) per output axis")
+        if x.dtype != torch.float32:
+            x = x.float()
+        if min(x.stride()) <= 0:
+            x = x.contiguous()
+        xs = x.stride()
+        arr_l, arr_i = ctypes.c_longlong * 3, ctypes.c_int * 3
+        strides = arr_l(*(xs[1 + p] for p in self.perm))
+        src_n, n_out = arr_i(*(self.src_shape[p] for p in self.perm)), arr_i(*self.out_shape)
+        lo, hi = arr_i(*(v[0] for v in valid)), arr_i(*(v[1] for v in valid))
+        with torch.cuda.device(x.device):
+            tabs = self._device_tables(x.device)
+            out = torch.empty(self.out_shape, dtype=torch.uint8, device=x.device)
+            call("u3d_grid_resample_argmax", x.data_ptr(), x.shape[0], strides, xs[0], src_n, n_out,
+                 *(tabs[i][0].data_ptr() for i in range(3)), *(tabs[i][1].data_ptr() for i in range(3)), lo, hi,
+                 out.data_ptr(), ops._stream())
+        return out
+
 
 def spacing_plan(shape, affine, pixdim=(1, 1, 2), axcodes="RAS", out_shape=None):
     """MONAI's Orientationd(axcodes) then Spacingd(pixdim) (defaults: diagonal False, scale_extent False, padding
@@ -754,3 +826,59 @@ def preprocess_case(image, label, affine, cid, pixdim=(1, 1, 2), axcodes="RAS", 
     image_a, label_a, info = body_crop(img, lab, cid, min_filter, min_filter_up)
     info.update(affine=out_affine, spacing=tuple(pixdim) if np.ndim(pixdim) else (pixdim,) * 3, plan=plan)
     return image_a, label_a, info
+
+
+# ------------------------------------------------------------------------------- predictions on the case's own grid
+KEEP_REC = 4                     # U3D_KEEP_RECORD: {components, voxels, kept voxels, first voxel of the kept component}
+
+
+def keep_largest_per_label(labels, num_labels=13, return_record=False):
+    """The per-organ cleanup every AMOS pipeline runs before it writes a label file, in one labelling
+    (u3d_ccl_keep_largest): labels [Z, Y, X] uint8, or int16 / int32 / int64 with values in 0..255, on the device. For
+    each label 1..num_labels (at most 255) the face-connected component with the most voxels is kept, on a tie the one
+    whose first voxel comes first in C order; the label's other voxels become 0; 0 and codes above num_labels stay.
+    Returns a tensor of the input's dtype and shape, with return_record also the device int32 [num_labels, 4] of
+    {components, voxels, kept voxels, linear index of the kept component's first voxel (-1: label absent)}. No host
+    read."""
+    if labels.dtype not in (torch.uint8, torch.int16, torch.int32, torch.int64):
+        raise ValueError(f"keep_largest_per_label: dtype {labels.dtype} (uint8, int16, int32 or int64)")
+    if not 1 <= int(num_labels) <= 255:
+        raise ValueError(f"keep_largest_per_label: num_labels={num_labels} must be in 1..255")
+    _volume3(labels, "keep_largest_per_label")
+    codes = labels.to(torch.uint8).contiguous()
+    Z, Y, X = codes.shape
+    with torch.cuda.device(codes.device):
+        out = torch.empty_like(codes)
+        rec = torch.empty((int(num_labels), KEEP_REC), dtype=torch.int32, device=codes.device)
+        ws = torch.empty(query("u3d_ccl_keep_largest_ws_bytes", codes.numel()), dtype=torch.uint8, device=codes.device)
+        call("u3d_ccl_keep_largest", codes.data_ptr(), Z, Y, X, int(num_labels), out.data_ptr(), rec.data_ptr(),
+             ws.data_ptr(), ops._stream())
+    out = out if labels.dtype == torch.uint8 else out.to(labels.dtype)
+    return (out, rec) if return_record else out
+
+
+def restore_prediction(pred, info, cleanup=False, num_labels=13):
+    """A prediction made on the grid of preprocess_case's image_a, carried to the case's own voxels: uint8
+    [info["plan"].src_shape], the file's index order. pred [C, z, y, x] float (logits or probabilities): the crop is
+    undone and the resampling inverted in one pass, plan.inverse().restrict_source(info["origin"], image_a's shape) and
+    apply_argmax: the scores are interpolated, then decided, and a voxel whose nearest voxel of the resampled grid lies
+    outside the crop is 0. pred [z, y, x] integer (a label map, values 0..255): zero-padded to the resampled grid and
+    sent through the nearest kernel with the whole inverse plan. cleanup: keep_largest_per_label(result, num_labels)."""
+    plan = info["plan"]
+    origin = tuple(int(v) for v in info["origin"])
+    inv = plan.inverse()
+    ops.require_device(pred)
+    if pred.dim() == 4 and pred.dtype.is_floating_point:
+        plan_w, valid = inv.restrict_source(origin, pred.shape[1:])
+        out = plan_w.apply_argmax(pred, valid)
+    elif pred.dim() == 3 and not pred.dtype.is_floating_point and pred.dtype != torch.bool:
+        if any(o + s > n for o, s, n in zip(origin, pred.shape, plan.out_shape)):
+            raise ValueError(f"restore_prediction: pred {tuple(pred.shape)} at {origin} is not inside the resampled grid "
+                             f"{plan.out_shape}")
+        full = torch.zeros(plan.out_shape, dtype=torch.uint8, device=pred.device)
+        full[tuple(slice(o, o + s) for o, s in zip(origin, pred.shape))] = pred.to(torch.uint8)
+        out = inv.apply(full, "nearest")
+    else:
+        raise ValueError(f"restore_prediction: pred {tuple(pred.shape)} {pred.dtype} must be [C, z, y, x] float scores "
+                         "or a [z, y, x] integer label map")
+    return keep_largest_per_label(out, num_labels) if cleanup else out
